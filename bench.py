@@ -16,7 +16,10 @@ has completed when the timed region closes); ``--exchange-mode serial`` waits fo
 the timed region the record's ``multi_gpu`` object adds, each measured on its own: ``raster_ms`` (no exchange),
 ``allreduce_ms`` (the exchange alone), ``serial_ms_per_step`` and ``overlapped_ms_per_step``.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying extra objects:
+Prints ONE JSON line on rank 0.  A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the headline (`value`, `ms_per_step`, per-step HIP events, `device_state`) and nothing else; ``--dump-outputs DIR``
+also writes what the last timed step returned as DIR/<name>.npy (``dump_outputs``).  With ``--full`` every other leg runs
+after the timed region (the ``multi_gpu`` legs above, the from-idle figure, stage times, …) and the line carries extra objects:
   "roofline"      the dominant kernel's algorithmic bytes ÷ its HIP-event duration (events on the stream the
                   kernels are launched on) vs 8 TB/s; ``traffic`` comes from a rocprofv3 PMC profile of this same
                   command committed under profiles/ and says so (``traffic_source``) — it is NOT measured in-run
@@ -237,18 +240,26 @@ class Workload:
         self.means2D = torch.zeros_like(self.means, requires_grad=need)
         self.leaves = (self.means, self.cov, self.op, self.shs, self.means2D) + ((self.view, self.proj, self.campos) if pose else ())
         self.pose = pose
+        # `--dump-outputs`: the step keeps what its forward returned (detached: the forward's buffers are not kept alive);
+        # the gradients of the last step stay on the leaves anyway
+        self.keep_outputs = False
+        self.last_outputs = None
 
     def step(self):
         if self.fwd_only:
             with torch.no_grad():
-                color, _, _ = self.rast(means3D=self.means, means2D=self.means2D, opacities=self.op, shs=self.shs,
-                                        cov3D_precomp=self.cov)
+                color, radii, depth = self.rast(means3D=self.means, means2D=self.means2D, opacities=self.op, shs=self.shs,
+                                                cov3D_precomp=self.cov)
+            if self.keep_outputs:
+                self.last_outputs = (color, radii, depth)
             return color
         for t in self.leaves:
             t.grad = None
-        color, _, _ = self.rast(means3D=self.means, means2D=self.means2D, opacities=self.op, shs=self.shs,
-                                cov3D_precomp=self.cov)
+        color, radii, depth = self.rast(means3D=self.means, means2D=self.means2D, opacities=self.op, shs=self.shs,
+                                        cov3D_precomp=self.cov)
         color.backward(self.dL)  # the upstream gradient dL/dcolor goes straight into the rasterizer's backward
+        if self.keep_outputs:
+            self.last_outputs = tuple(None if t is None else t.detach() for t in (color, radii, depth))
         return color
 
     def fwd_bwd_event_times(self, n: int = 30) -> dict:
@@ -543,6 +554,56 @@ def timed_steps(fn, steps: int, warmup: int, dev, barrier=None, finish=None, pre
     return elapsed, [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
 
 
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_GAUSSIAN_ROWS = 65_536      # per-Gaussian arrays: this many rows, the same seeded rows in every array
+DUMP_IMAGE_ELEMS = 1 << 23       # image arrays up to this many values whole, larger ones a seeded sample of that many
+
+
+def dump_outputs(wl, out_dir: str) -> dict:
+    """`--dump-outputs DIR`: what the timed path handed its caller in its LAST timed step — the forward's image, radii and
+    depth image, and the gradients the backward left on the inputs — as DIR/<name>.npy in float32.  The inputs are
+    seeded, so two builds run with the same arguments can be compared array for array.  Per-Gaussian arrays are a fixed,
+    seeded sample of DUMP_GAUSSIAN_ROWS rows (the same rows in each); the whole set stays within DUMP_BUDGET_BYTES.
+    Returns {name: shape}."""
+    import numpy as np
+    color, radii, depth = wl.last_outputs
+    rows = None
+    if wl.P > DUMP_GAUSSIAN_ROWS:
+        pick = np.sort(np.random.default_rng(0).choice(wl.P, DUMP_GAUSSIAN_ROWS, replace=False))
+        rows = torch.from_numpy(pick).to(wl.dev)
+
+    def per_gaussian(t):
+        return t if rows is None else t.index_select(0, rows)
+
+    def image(t):
+        if t.numel() <= DUMP_IMAGE_ELEMS:
+            return t
+        pick = np.sort(np.random.default_rng(1).choice(t.numel(), DUMP_IMAGE_ELEMS, replace=False))
+        return t.reshape(-1).index_select(0, torch.from_numpy(pick).to(t.device))
+
+    named = [("color", color, image), ("depth", depth, image), ("radii", radii, per_gaussian)]
+    if not wl.fwd_only:
+        named += [("grad_means3D", wl.means.grad, per_gaussian), ("grad_cov3D_precomp", wl.cov.grad, per_gaussian),
+                  ("grad_opacities", wl.op.grad, per_gaussian), ("grad_shs", wl.shs.grad, per_gaussian),
+                  ("grad_means2D", wl.means2D.grad, per_gaussian)]
+        if wl.pose:
+            named += [("grad_viewmatrix", wl.view.grad, None), ("grad_projmatrix", wl.proj.grad, None),
+                      ("grad_campos", wl.campos.grad, None)]
+    arrays = {}
+    for name, t, sample in named:
+        if t is None:
+            continue
+        t = t.detach()
+        arrays[name] = (sample(t) if sample else t).to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 # ---------------------------------------------------------------------------------------------------------
 # CPU baselines (rank 0, N = 1 only; test infrastructure used as the reported baseline, never as the product)
 # ---------------------------------------------------------------------------------------------------------
@@ -748,10 +809,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C3", help="key of ggrt_official_amd.synthetic.CONFIGS")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-graph", action="store_true", help="skip the informational HIP-graph replay leg")
-    ap.add_argument("--no-callsite", action="store_true", help="skip the informational GGRt-shape call-site leg")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C5'/C4'/non-uniform-C3 records (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg of the record: N>1 exchange legs, from-idle, stage "
+                         "times, rooflines, list-hint, call-site, secondary shapes, stream legs, CPU baselines.  "
+                         "Without it the run sets up, warms up, times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (image, radii, depth, input gradients; per-Gaussian "
+                         "arrays a seeded sample) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-graph", action="store_true", help="--full: skip the informational HIP-graph replay leg")
+    ap.add_argument("--no-callsite", action="store_true", help="--full: skip the informational GGRt-shape call-site leg")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C5'/C4'/non-uniform-C3 records (N = 1 only)")
     ap.add_argument("--grad-buffer-floats", type=int, default=65_000_000,
                     help="N>1: size of the flat fp32 stand-in for GGRt's encoder + pose-network gradients that is "
                          "mean-all-reduced every step together with the camera gradient (SURVEY.md §5: ≈65 M floats "
@@ -760,12 +828,12 @@ def main():
                     help="N>1, the timed loop: `overlap` issues each step's all-reduce asynchronously so that it runs "
                          "behind the next frame's rasterization (all of them complete inside the timed region); "
                          "`serial` waits for it inside the step.  Both are reported in `multi_gpu` either way")
-    ap.add_argument("--profile-steps", type=int, default=5, help="extra untimed steps with per-stage HIP events")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: extra untimed steps with per-stage HIP events")
     ap.add_argument("--prewarm-ms", type=float, default=60.0,
                     help="run the step for this long BEFORE the W warm-up steps: an MI355X that was idle for >= 10 ms runs "
                          "its first ~22 ms of work 3-10 %% slower whatever the work is (power-state ramp, "
                          "profiles/r04_ramp_probe.txt) — W = 5 steps of 0.9 ms end inside it.  The record says so "
-                         "(`device_state`) and carries the from-idle figure beside the headline; 0 = off")
+                         "(`device_state`; with --full it also carries the from-idle figure beside the headline); 0 = off")
     ap.add_argument("--dist-backend", default=None,
                     help="debug: process-group backend (default: nccl = RCCL).  `gloo` together with `--device 0` "
                          "lets several ranks share ONE GPU to dry-run the N>1 control flow on a 1-GPU box")
@@ -801,7 +869,8 @@ def main():
     assert torch.cuda.current_device() == local, (torch.cuda.current_device(), local)
     rank_devices = parallel.rank_device_report(dev, shared_ok=args.device is not None) if dist_on else None
     cfg = CONFIGS[args.config]
-    wl = Workload(args.config, cfg, dev, seed=rank, keep_cpu_scene=(rank == 0 and world == 1))  # one frame per rank
+    wl = Workload(args.config, cfg, dev, seed=rank, keep_cpu_scene=(args.full and rank == 0 and world == 1))  # one frame per rank
+    wl.keep_outputs = bool(args.dump_outputs)
     W, H, P = wl.W, wl.H, wl.P
 
     # ---- the exchange (N > 1): ONE flat buffer = stand-in parameter gradients + this step's camera gradient -----
@@ -861,6 +930,42 @@ def main():
     peak_bytes = torch.cuda.max_memory_allocated(dev)
     elapsed = parallel.max_over_ranks(elapsed, dev)
     log(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.3f} ms/step")
+    D = cfg["sh_degree"]
+    ms_per_step = elapsed / args.steps * 1e3
+    device_state = {"prewarm_ms": round(prewarm_ms, 1), "prewarm_steps": prewarm_steps,
+                    "python_gc": "paused inside every timed bracket (collected before the prewarm)",
+                    "note": "the timed region is W warm-up + K steps as the contract says; before it the step ran for "
+                            "`prewarm_ms` so that the device is in its sustained power state (from idle the first ~22 ms "
+                            "of ANY work run 3-10 % slower: tools/ramp_probe.py, profiles/r04_ramp_probe.txt)"}
+    rec = None
+    if rank == 0:
+        if args.dump_outputs:
+            shapes = dump_outputs(wl, args.dump_outputs)
+            log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
+        wl.keep_outputs = False
+        rec = {
+            "metric": "Gaussian raster fwd+bwd Mpix/s @1M Gaussians 1080p",
+            "value": round(world * W * H * args.steps / elapsed / 1e6, 3),
+            "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.config}: {P} Gaussians, {W}x{H}, SH deg {D}, profile {cfg['profile']}, "
+                                   f"fwd+bwd incl. camera gradient, 1 frame per GPU" +
+                                   (f", one RCCL mean all-reduce per step of {G} stand-in parameter-gradient floats + the "
+                                    f"camera gradient ({args.exchange_mode}, {args.exchange_chunks} chunks)" if dist_on else ""),
+                       "parallelism": f"frames x{world}"},
+            "step_ms_hip_events": percentiles(per_step),
+            "device_state": device_state,
+        }
+        if dist_on:
+            rec["value_note"] = ("value = frames·W·H ÷ the step incl. the one mean all-reduce of the stand-in parameter gradients "
+                                 f"({(G + 35) * 4 / 1e6:.0f} MB, {args.exchange_mode}); scaling_basis names the figure that scales "
+                                 "with the path itself")
+    if not args.full:            # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(rec), flush=True)
+        parallel.shutdown()
+        return
 
     # ---- N > 1: the pieces of the step, each measured on its own (after the timed region) -------------------
     multi = None
@@ -942,11 +1047,6 @@ def main():
 
     # informational: the same K steps + W warm-up started from an IDLE device (0.5 s of sleep) — what a caller who renders
     # one burst now and then gets, and what this bench reported before `--prewarm-ms` existed
-    device_state = {"prewarm_ms": round(prewarm_ms, 1), "prewarm_steps": prewarm_steps,
-                    "python_gc": "paused inside every timed bracket (collected before the prewarm)",
-                    "note": "the timed region is W warm-up + K steps as the contract says; before it the step ran for "
-                            "`prewarm_ms` so that the device is in its sustained power state (from idle the first ~22 ms "
-                            "of ANY work run 3-10 % slower: tools/ramp_probe.py, profiles/r04_ramp_probe.txt)"}
     if world == 1:
         time.sleep(0.5)
         cold_n = min(args.steps, 20)
@@ -1114,8 +1214,6 @@ def main():
             log(f"list-hint legs skipped: {type(e).__name__}: {e}")
 
     if rank == 0:
-        D = cfg["sh_degree"]
-        ms_per_step = elapsed / args.steps * 1e3
         rf = wl.rooflines(stages, N, N_built)
         dom = rf["roofline"]["kernel"]
         kname = {"bwd_blend": "blend_bwd_kernel", "fwd_blend": "blend_fwd_kernel",
@@ -1165,28 +1263,16 @@ def main():
                     r_["frac_basis"] = "kernel_ms (HIP events of this run: the committed kernel trace is of other sources)"
         except Exception as e:
             log(f"rocprof kernel time skipped: {type(e).__name__}: {e}")
-        rec = {
-            "metric": "Gaussian raster fwd+bwd Mpix/s @1M Gaussians 1080p",
-            "value": round(world * W * H * args.steps / elapsed / 1e6, 3),
-            "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.config}: {P} Gaussians, {W}x{H}, SH deg {D}, profile {cfg['profile']}, "
-                                   f"fwd+bwd incl. camera gradient, 1 frame per GPU" +
-                                   (f", one RCCL mean all-reduce per step of {G} stand-in parameter-gradient floats + the "
-                                    f"camera gradient ({args.exchange_mode}, {args.exchange_chunks} chunks)" if dist_on else ""),
-                       "num_rendered": N, "num_rendered_built": N_built,
-                       "num_rendered_note": "num_rendered = N_dup by the reference's emit rule (3-sigma square), which SURVEY §8(d)'s "
-                                            "algorithmic bytes are defined with; num_rendered_built = what the default build "
-                                            "lists (tight tile rects, same outputs bit for bit)",
-                       "parallelism": f"frames x{world}"},
-            "step_ms_hip_events": percentiles(per_step),
-            "device_state": device_state,
+        rec["config"].update({"num_rendered": N, "num_rendered_built": N_built,
+                              "num_rendered_note": "num_rendered = N_dup by the reference's emit rule (3-sigma square), which "
+                                                   "SURVEY §8(d)'s algorithmic bytes are defined with; num_rendered_built = what "
+                                                   "the default build lists (tight tile rects, same outputs bit for bit)"})
+        rec.update({
             "stages_ms": {k: round(v, 4) for k, v in stages.items()},
             # (fwd_colour_side_stream_ms ran BESIDE the sort / tile-list stages, on the forward's side stream: not a term)
             "t_fwd_ms": round(sum(v for k, v in stages.items() if k.startswith("fwd_") and "side_stream" not in k), 4),
             "t_bwd_ms": round(sum(v for k, v in stages.items() if k.startswith("bwd_")), 4),
-        }
+        })
         # the same two figures without the stage profiling's synchronisations (the stage sum contains the host's wait for
         # num_rendered, which the default mode's list-size guess removes): HIP events around forward and backward
         try:
@@ -1274,9 +1360,6 @@ def main():
                 rec["ms_per_step_raster_plus_camera_grad"] = cam_only[0]["overlapped_ms_per_step"]
             pcis = [r.get("pci") for r in (rank_devices or [])]
             rec["ranks_on_distinct_gpus"] = bool(pcis) and None not in pcis and len(set(pcis)) == len(pcis)
-            rec["value_note"] = ("value = frames·W·H ÷ the step incl. the one mean all-reduce of the stand-in parameter gradients "
-                                 f"({(G + 35) * 4 / 1e6:.0f} MB, {args.exchange_mode}); scaling_basis names the figure that scales "
-                                 "with the path itself")
         if world == 1 and not args.no_callsite:
             # informational: GGRt's own shape through the call-site layer (scripts/callsite_bench.py)
             try:

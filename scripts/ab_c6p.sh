@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev, on the GPU box: large / multi-view shapes under the colour kernel's throttle settings
 cd $GRAFT_REPO_ROOT
-run() { python bench.py --config $1 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "^\[bench.*(stages|timed)" | cut -c1-330; }
+run() { python bench.py --full --config $1 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "^\[bench.*(stages|timed)" | cut -c1-330; }
 for CFG in C6p; do
   echo "== $CFG one kernel"; GGR_SPLIT_COLOUR=0 run $CFG
   echo "== $CFG adaptive"; run $CFG

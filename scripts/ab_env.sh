@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT
 CFG=${AB_CONFIG:-C3}
 for e in "$@"; do
-  out=$(env $e python $R/bench.py --config $CFG --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1)
+  out=$(env $e python $R/bench.py --full --config $CFG --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1)
   st=$(echo "$out" | grep "stages:" | sed 's/.*stages: //; s/fwd_//g; s/_ms=/=/g')
   ms=$(echo "$out" | grep -o '"ms_per_step": [0-9.]*' | head -1)
   fw=$(echo "$out" | grep -o '"t_fwd_ms_events": [0-9.]*' | head -1)

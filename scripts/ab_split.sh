@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 FORKS=$1; shift
 LIST=$1; shift
-run() { python bench.py --config $1 --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "stages|timed|Error|error" | cut -c1-330 | grep -v '^{'; }
+run() { python bench.py --full --config $1 --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "stages|timed|Error|error" | cut -c1-330 | grep -v '^{'; }
 for CFG in "$@"; do
   echo "== $CFG one kernel"
   GGR_SPLIT_COLOUR=0 run $CFG

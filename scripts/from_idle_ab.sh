@@ -3,5 +3,5 @@
 cd $GRAFT_REPO_ROOT
 for SPLIT in 1 0 1 0; do
   echo "== split=$SPLIT"
-  GGR_SPLIT_COLOUR=$SPLIT python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "from idle|timed" | cut -c1-300
+  GGR_SPLIT_COLOUR=$SPLIT python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "from idle|timed" | cut -c1-300
 done

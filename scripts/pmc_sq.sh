@@ -4,9 +4,10 @@
 # usage: scripts/pmc_sq.sh <tag> [bench args...]
 set -u
 TAG=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp; cd /tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/pmc_sq_$TAG; mkdir -p $O
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-graph --no-callsite $*"
+CMD="python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-graph --no-callsite $*"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU" \
            "SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY" \

@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-callsite --no-graph"
+BENCH="python $R/bench.py --full --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-callsite --no-graph"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- $BENCH > $OUT/trace.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o fetch -- $BENCH > $OUT/fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o write -- $BENCH > $OUT/write.log 2>&1

@@ -9,6 +9,6 @@ for d in $R/gpurun_variants/*/; do
   n=$(basename $d)
   cp $d/libggr_raster.so $R/ggrt_official_amd/libggr_raster.so
   scripts/quick_trace.sh var_$n > /dev/null 2>&1
-  echo "== $n"; grep -E "$PAT" $R/gpurun_out/var_$n/c3_kernel_stats.txt | cut -c1-110
+  echo "== $n"; grep -E "$PAT" $R/build/traces/var_$n/c3_kernel_stats.txt | cut -c1-110
 done
 cp /tmp/base.so $R/ggrt_official_amd/libggr_raster.so

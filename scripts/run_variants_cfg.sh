@@ -5,7 +5,7 @@ CFG=${1:-C5p}
 R=$GRAFT_REPO_ROOT
 export GGR_SKIP_SOURCE_HASH=1   # variants carry the hash of their own flags (_build.source_hash)
 cp $R/ggrt_official_amd/libggr_raster.so /tmp/base.so
-run() { python bench.py --config $CFG --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "^\[bench.*(stages|timed)" | cut -c1-330; }
+run() { python bench.py --full --config $CFG --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "^\[bench.*(stages|timed)" | cut -c1-330; }
 echo "== base"; run
 for d in $R/gpurun_variants/*/; do
   n=$(basename $d)

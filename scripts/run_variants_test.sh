@@ -9,6 +9,6 @@ for d in $R/gpurun_variants/*/; do
   cp $d/libggr_raster.so $R/ggrt_official_amd/libggr_raster.so
   echo "== $n"
   python -m pytest $SEL -x -q 2>&1 | tail -3
-  python bench.py --config $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "stages|timed"
+  python bench.py --full --config $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-callsite --no-graph 2>&1 | grep -E "stages|timed"
 done
 cp /tmp/base.so $R/ggrt_official_amd/libggr_raster.so

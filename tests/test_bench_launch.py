@@ -94,3 +94,41 @@ def test_byte_model_of_the_built_kernels():
     assert ab["bwd_preprocess"] == 1_000_000 * (40 + 192) + 1_000_000 * (52 + 192)
     assert ab["bwd_preprocess_moved"] == 1_000_000 * 156 + 1_000_000 * 244 == 400_000_000
     assert ab["tile_sort_compulsory"] == 8_000_000 * 12 and ab["tile_scatter_pairs_compulsory"] == 8_000_000 * 8 + 12_000_000
+
+
+def test_dump_outputs_writes_the_last_step_as_float32_samples(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: every array the step hands its caller, float32; per-Gaussian arrays share one seeded row sample,
+    images beyond the cap are a seeded sample too, and a set over the budget is refused before anything is written."""
+    import types
+    import numpy as np
+    import torch
+    bench = _bench()
+    P, H, W = 100_000, 6, 8
+    ramp = lambda *shape: torch.arange(P, dtype=torch.float32).reshape(P, *[1] * len(shape)).expand(P, *shape).contiguous()
+    leaf = lambda g: types.SimpleNamespace(grad=g)
+    wl = types.SimpleNamespace(
+        P=P, dev=torch.device("cpu"), fwd_only=False, pose=True,
+        last_outputs=(torch.rand(3, H, W), torch.arange(P, dtype=torch.int32), torch.rand(H, W)),
+        means=leaf(ramp(3)), cov=leaf(ramp(6)), op=leaf(ramp(1)), shs=leaf(ramp(16, 3)), means2D=leaf(ramp(3)),
+        view=leaf(torch.eye(4)), proj=leaf(torch.eye(4)), campos=leaf(torch.ones(3)))
+    shapes = bench.dump_outputs(wl, str(tmp_path / "a"))
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert set(got) == {"color", "depth", "radii", "grad_means3D", "grad_cov3D_precomp", "grad_opacities", "grad_shs",
+                        "grad_means2D", "grad_viewmatrix", "grad_projmatrix", "grad_campos"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["color"], wl.last_outputs[0].numpy()) and got["grad_campos"].shape == (3,)
+    rows = got["radii"]
+    assert rows.shape == (bench.DUMP_GAUSSIAN_ROWS,) and np.all(np.diff(rows) > 0)
+    for n in ("grad_means3D", "grad_cov3D_precomp", "grad_opacities", "grad_shs", "grad_means2D"):
+        assert got[n].shape[0] == rows.shape[0] and np.all(got[n].reshape(rows.shape[0], -1) == rows[:, None]), n
+    # the same arguments, the same sample
+    bench.dump_outputs(wl, str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "grad_shs.npy"), got["grad_shs"])
+    monkeypatch.setattr(bench, "DUMP_IMAGE_ELEMS", 40)
+    bench.dump_outputs(wl, str(tmp_path / "c"))
+    c = np.load(tmp_path / "c" / "color.npy")
+    assert c.shape == (40,) and np.all(np.isin(c, wl.last_outputs[0].numpy()))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    with pytest.raises(RuntimeError, match="budget"):
+        bench.dump_outputs(wl, str(tmp_path / "d"))
+    assert not (tmp_path / "d").exists()

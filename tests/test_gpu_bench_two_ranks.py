@@ -27,8 +27,8 @@ def _free_port():
 @pytest.mark.parametrize("mode", ["overlap", "serial"])
 def test_bench_two_ranks_share_one_gpu(mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--config", "C2", "--dist-backend", "gloo", "--device", "0", "--grad-buffer-floats", "300000",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps",
+           "2", "--warmup", "1", "--config", "C2", "--dist-backend", "gloo", "--device", "0", "--grad-buffer-floats", "300000",
            "--exchange-mode", mode, "--profile-steps", "1"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=800)
@@ -62,8 +62,8 @@ def test_bench_one_rank_over_rccl():
     """VERDICT r2 missing #4: the RCCL branch itself (`backend="nccl"`, `device_id=`, `ReduceOp.AVG`, the chunked
     asynchronous exchange) executed on the 1-GPU box: one rank under torch.distributed.run with a forced process group."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--config", "C2", "--force-dist", "--grad-buffer-floats", "1000000", "--profile-steps", "1",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps",
+           "2", "--warmup", "1", "--config", "C2", "--force-dist", "--grad-buffer-floats", "1000000", "--profile-steps", "1",
            "--no-cpu-baseline", "--no-secondary", "--no-callsite", "--no-graph"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=800)
@@ -87,7 +87,7 @@ def test_bench_launches_its_own_ranks():
     """plain `python bench.py --gpus 2` (no launcher, WORLD_SIZE / RANK unset — the form the driver used
     for N = 1) starts its two ranks itself and prints ONE contract line with n_gpus == 2; the record carries the
     grad-buffer sweep that shows where the step turns exchange-bound."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--device", "0", "--steps",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--device", "0", "--steps",
            "2", "--warmup", "1", "--config", "C2", "--grad-buffer-floats", "300000", "--profile-steps", "1"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE", "GROUP_RANK")}

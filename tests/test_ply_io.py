@@ -1,6 +1,8 @@
 """`.ply` interchange: byte layout, round trips, and the export's scene normalisation
 (reference ``ply_export.py:12-23,26-92``) checked against scipy's rotation conversions."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -110,18 +112,29 @@ def test_export_normalises_like_the_reference(tmp_path):
     assert (np.abs(t[:, 0:3]) <= 1.0 + 1e-6).mean() > 0.9
 
 
-GOLDEN_EXPORT = os.path.join(os.path.dirname(__file__), "golden", "ply_export_scene.npz")
+GOLDEN_EXPORT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ply_export_scene.npz")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_export_payload_is_byte_identical_to_the_reference(tmp_path):
     """`tests/golden/ply_export_scene.npz` (tests/golden/make_decoder_golden.py::ply_golden): the structured vertex array
     the REFERENCE's own `export_ply` (ply_export.py:26-92, imported in the build container with a recording `plyfile`
     stub) handed to `PlyElement.describe(..., "vertex")` for a seeded scene.  The build's exporter must write exactly
-    those bytes after its header, and name the columns as the reference's dtype does."""
+    those bytes after its header, and name the columns as the reference's dtype does.  The means pass through a BLAS
+    matrix product whose float32 rounding depends on the code path MKL picks for the CPU: the table was recorded on MKL's
+    CPU-independent path (MKL_CBWR=COMPATIBLE), and the export runs on that path here, in a process of its own."""
     z = np.load(GOLDEN_EXPORT, allow_pickle=False)
-    t = lambda k: torch.from_numpy(z["in_" + k])
     p = tmp_path / "sub" / "scene.ply"
-    ply_io.export_ply(t("extrinsics"), t("means"), t("scales"), t("rotations"), t("harmonics"), t("opacities"), p)
+    code = ("import sys, numpy as np, torch\n"
+            f"sys.path.insert(0, {ROOT!r})\n"
+            "from ggrt_official_amd import ply_io\n"
+            f"z = np.load({GOLDEN_EXPORT!r}, allow_pickle=False)\n"
+            "t = lambda k: torch.from_numpy(z['in_' + k])\n"
+            "ply_io.export_ply(t('extrinsics'), t('means'), t('scales'), t('rotations'), t('harmonics'), t('opacities'), "
+            f"{str(p)!r})\n")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MKL_CBWR="COMPATIBLE"), stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:]
     blob = p.read_bytes()
     cut = blob.index(b"end_header\n") + len(b"end_header\n")
     ref = z["table"]
