@@ -70,6 +70,15 @@ class GgrBackwardOut(C.Structure):
         ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p), ("stage_ms", C.c_void_p),
     ]
 
+class GgrForwardOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("antialiasing", C.c_int32)]
+
+
+def forward_options(antialiasing: bool = False) -> GgrForwardOptions:
+    """The options of ggr_forward_opt / ggr_forward_views_opt (include/ggr_raster.h), struct_size filled in."""
+    return GgrForwardOptions(struct_size=C.sizeof(GgrForwardOptions), antialiasing=int(bool(antialiasing)))
+
+
 FWD_STAGES = ["preprocess", "depth_sort", "tile_count", "tile_scatter", "blend", "colour_side_stream", "tile_sort"]
 DEPTH_SORT = {"auto": 0, "global": 1, "per_tile": 2, "global_3pass": 0x101}
 DEPTH_SORT_NO_BUCKETS = 0x100      # IN flag: never the global sort's bucket form (include/ggr_raster.h)
@@ -104,6 +113,11 @@ SYMBOLS = [
                                     C.POINTER(GgrForwardOut), ALLOC_FN, C.c_void_p, C.c_void_p]),
     ("ggr_backward_views", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrBackwardIn),
                                      C.POINTER(GgrBackwardOut), C.c_void_p]),
+    ("ggr_forward_opt", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrForwardOptions), C.POINTER(GgrForwardIn),
+                                  C.POINTER(GgrForwardOut), ALLOC_FN, C.c_void_p, C.c_void_p]),
+    ("ggr_forward_views_opt", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrForwardOptions), C.POINTER(GgrViews),
+                                        C.POINTER(GgrForwardIn), C.POINTER(GgrForwardOut), ALLOC_FN, C.c_void_p,
+                                        C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),

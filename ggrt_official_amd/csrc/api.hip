@@ -73,6 +73,19 @@ struct StageTimer {
     ~StageTimer() { finish(); }
 };
 
+// GgrForwardOptions: NULL = the defaults of ggr_forward; checked before anything is enqueued
+int validate_options(const GgrForwardOptions* opt, int* antialiasing) {
+    *antialiasing = 0;
+    if (!opt) return GGR_OK;
+    if (opt->struct_size < (int32_t)(offsetof(GgrForwardOptions, antialiasing) + sizeof(int32_t)))
+        return fail(GGR_E_INVALID, "GgrForwardOptions.struct_size %d is smaller than the %d bytes of its fields", (int)opt->struct_size,
+                    (int)(offsetof(GgrForwardOptions, antialiasing) + sizeof(int32_t)));
+    if (opt->antialiasing != 0 && opt->antialiasing != 1)
+        return fail(GGR_E_INVALID, "GgrForwardOptions.antialiasing must be 0 or 1, not %d", (int)opt->antialiasing);
+    *antialiasing = opt->antialiasing;
+    return GGR_OK;
+}
+
 int validate(const GgrSettings* st, const GgrForwardIn* in) {
     if (!st || !in) return fail(GGR_E_INVALID, "null settings / inputs");
     if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0)
@@ -461,7 +474,7 @@ namespace {
 // the tiles of the views are stacked (ggr_common.h ViewSet): one preprocess launch, ONE depth sort over the V·P keys,
 // one tile-list build over the V·T tiles, one blend launch.
 int forward_impl(const GgrSettings* st, const ViewSet& vs, const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc,
-                 void* alloc_ctx, void* stream) {
+                 void* alloc_ctx, void* stream, int antialiasing) {
     if (!out || !out->out_color || !out->geom_buffer || !out->image_buffer || !alloc)
         return fail(GGR_E_INVALID, "null output / buffer / allocator");
     if (st->num_points > 0 && !out->radii) return fail(GGR_E_INVALID, "null radii");
@@ -528,7 +541,8 @@ int forward_impl(const GgrSettings* st, const ViewSet& vs, const GgrForwardIn* i
     //    the side stream beside the latency-bound sort / tile-list kernels (which leave HBM and most CUs idle) and is joined
     //    in front of the blend.  Not while the caller's stream is being captured into a graph (a thread-local side stream
     //    would be pulled into the capture), not in debug mode (one kernel at a time), not for precomputed colours.
-    const InputForm inf = input_form(st, in, vs.sets);
+    InputForm inf = input_form(st, in, vs.sets);
+    inf.antialiasing = antialiasing;   // (preprocess_fwd also records it in the geometry buffer for the backward)
     SideStream* side = nullptr;
     // … nor for more than GGR_SPLIT_MAX_POINTS Gaussians per set: the colour kernel's bytes grow with them faster than the
     // window beside the binning does (C6′, 4.9 M Gaussians of 25 coefficients: 1.9 GB to move within ≈ 0.47 ms — at that rate
@@ -868,7 +882,8 @@ int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn*
                                out->dL_dopacities, out->dL_dshs, out->dL_dcolors_precomp, out->dL_dcov3D,
                                out->dL_dscales, out->dL_drotations, in->fwd.aux_precomp ? out->dL_daux : nullptr,
                                npose ? sc.pose_acc : nullptr, out->dL_dviewmatrix, out->dL_dprojmatrix,
-                               out->dL_dcampos, input_form(st, &in->fwd, vs.sets, out->dL_dshs), in->fwd.cov3D_precomp ? 1 : 0, s);
+                               out->dL_dcampos, input_form(st, &in->fwd, vs.sets, out->dL_dshs), in->fwd.cov3D_precomp ? 1 : 0,
+                               in->fwd.opacities, g.counters + GGR_CTR_ANTIALIAS /*the forward's mode*/, s);
     KCHECK(dbg, s, "preprocess_bwd");
     tm.mark(GGR_BWD_PREPROCESS);
     return GGR_OK;
@@ -878,12 +893,20 @@ int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn*
 
 extern "C" {
 
+int ggr_forward_opt(const GgrSettings* st, const GgrForwardOptions* opt, const GgrForwardIn* in, GgrForwardOut* out,
+                    GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+    g_err[0] = 0;
+    int aa = 0;
+    int rc = validate_options(opt, &aa);
+    if (rc) return rc;
+    rc = validate(st, in);
+    if (rc) return rc;
+    return forward_impl(st, single_view(st, in), in, out, alloc, alloc_ctx, stream, aa);
+}
+
 int ggr_forward(const GgrSettings* st, const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc,
                 void* alloc_ctx, void* stream) {
-    g_err[0] = 0;
-    int rc = validate(st, in);
-    if (rc) return rc;
-    return forward_impl(st, single_view(st, in), in, out, alloc, alloc_ctx, stream);
+    return ggr_forward_opt(st, nullptr, in, out, alloc, alloc_ctx, stream);
 }
 
 int ggr_backward(const GgrSettings* st, const GgrBackwardIn* in, GgrBackwardOut* out, void* stream) {
@@ -894,14 +917,22 @@ int ggr_backward(const GgrSettings* st, const GgrBackwardIn* in, GgrBackwardOut*
     return backward_impl(st, single_view(st, &in->fwd), in, out, stream);
 }
 
-int ggr_forward_views(const GgrSettings* st, const GgrViews* views, const GgrForwardIn* in, GgrForwardOut* out,
-                      GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+int ggr_forward_views_opt(const GgrSettings* st, const GgrForwardOptions* opt, const GgrViews* views, const GgrForwardIn* in,
+                          GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream) {
     g_err[0] = 0;
-    int rc = validate(st, in);
+    int aa = 0;
+    int rc = validate_options(opt, &aa);
+    if (rc) return rc;
+    rc = validate(st, in);
     if (rc) return rc;
     ViewSet vs;
     if ((rc = view_set(st, views, &vs)) != 0) return rc;
-    return forward_impl(st, vs, in, out, alloc, alloc_ctx, stream);
+    return forward_impl(st, vs, in, out, alloc, alloc_ctx, stream, aa);
+}
+
+int ggr_forward_views(const GgrSettings* st, const GgrViews* views, const GgrForwardIn* in, GgrForwardOut* out,
+                      GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+    return ggr_forward_views_opt(st, nullptr, views, in, out, alloc, alloc_ctx, stream);
 }
 
 int ggr_backward_views(const GgrSettings* st, const GgrViews* views, const GgrBackwardIn* in, GgrBackwardOut* out,

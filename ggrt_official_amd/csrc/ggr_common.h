@@ -3,7 +3,8 @@
 // Data layout in HBM (all caller-owned, carved out of opaque buffers; 256-B aligned sections)
 //
 //   geom buffer   (per Gaussian, P entries; kept for backward)
-//     splat[P]         2 × float4 = 32 B  {x, y, conic.xx, conic.xy | conic.yy, opacity, f, qmax}
+//     splat[P]         2 × float4 = 32 B  {x, y, conic.xx, conic.xy | conic.yy, opacity, f, qmax}  (opacity: × the anti-aliasing
+//                      factor when the forward is anti-aliased — GgrForwardOptions, preprocess.hip — and qmax from that value)
 //     colour[P]        1 × float4 = 16 B  {r, g, b, 0}
 //                      together everything the blend kernels need for a list entry (f = view-space z or the
 //                      caller's aux feature; qmax = 2·ln(255·opacity): the largest dᵀ·conic·d at which α still
@@ -40,6 +41,9 @@
 #define GGR_ALPHA_MIN (1.0f / 255.0f)
 #define GGR_ALPHA_MAX 0.99f
 #define GGR_T_MIN 0.0001f
+// anti-aliasing (GgrForwardOptions.antialiasing): opacity · sqrt(max(GGR_AA_MIN_RATIO, det(Σ) / det(Σ + GGR_DILATION·I))) —
+// upstream's constants (its 2D Mip filter: h_var = 0.3, the clamp 0.000025)
+#define GGR_AA_MIN_RATIO 0.000025f
 
 // depth sort geometry (binning.hip): 512 threads × 8 items = 4096 keys per sort tile (8 ranking rounds per wave: the
 // rounds are a chain of dependent LDS round trips, and a tile per CU leaves room for 8 waves)
@@ -183,6 +187,9 @@ static inline size_t ggr_sort_block_min_at(size_t n, size_t S = 1) { return ggr_
 static inline size_t ggr_sort_bucket_ranges_at(size_t n, size_t S = 1) { return (ggr_sort_block_min_at(n, S) + ggr_sort_block_words(n) + 1) & ~(size_t)1; }
 static inline size_t ggr_sort_hist_words(size_t n, size_t S = 1) { return ggr_sort_bucket_ranges_at(n, S) + S * 2 * GGR_SORT_MAX_BINS; }
 
+// counters word in which preprocess_fwd records GgrForwardOptions.antialiasing for the backward of the same frame (0 / 1;
+// preprocess_bwd reads it on the device: no read-back, and a backward cannot differentiate another mode than its forward's)
+#define GGR_CTR_ANTIALIAS 8
 struct GeomLayout {
     float4* splat;    // [P][2]
     float4* colour;   // [P]
@@ -195,7 +202,7 @@ struct GeomLayout {
     uint32_t* vals_a;
     uint32_t* vals_b;
     uint32_t* hist;       // sort work area (ggr_sort_hist_words)
-    uint32_t* counters;   // [64]
+    uint32_t* counters;   // [64]: words 0-4 the tile-list builder's / sorts' (api.hip), GGR_CTR_ANTIALIAS the forward's mode
     size_t bytes;
 };
 
@@ -219,7 +226,7 @@ static inline GeomLayout ggr_carve_geom(void* base, size_t P, size_t segments = 
     L.vals_a = (uint32_t*)take(Pp * 4);
     L.vals_b = (uint32_t*)take(Pp * 4);
     L.counters = (uint32_t*)take(64 * 4);  // (before the sort area: its offset must not depend on `segments`)
-    L.hist = (uint32_t*)take(ggr_sort_hist_words(Pp, segments) * 4);
+    L.hist = (uint32_t*)take(ggr_sort_hist_words(Pp, segments) * 4);   // (= counters + 64: preprocess_fwd clears both at once)
     L.sh_jac = with_jac ? (float4*)take(Pp * 48) : nullptr;
     L.bytes = o;
     return L;
@@ -316,6 +323,8 @@ struct InputForm {
     int sc_x0, sc_y0, sc_x1, sc_y1;  // GgrSettings.scissor in TILES, half-open, inside the tile grid (whole grid = none)
     int sh_aligned;            // every set's SH rows (and gradient rows) start 16-B aligned: flat float4 staging allowed
     int tight_rects;           // 1 (default): tile rects clipped to the α ≥ 1/255 ellipse's bounding box (ggr_tighten_rect)
+    int antialiasing;          // 1: opacity scaled for the dilation (GgrForwardOptions; forward only — the backward reads the
+                               //    mode the forward recorded, GGR_CTR_ANTIALIAS)
 };
 
 // ---- TIGHT tile rects (round 3; restated in oracle/ggr_oracle.c `tighten_rect`, same operations in the same order) ----
@@ -495,7 +504,8 @@ void launch_preprocess_bwd(int P, int D, int M, const float* means3D, const floa
                            float* dL_drotations, float* dL_daux, float* pose_acc /*null: no camera gradient*/,
                            float* dL_dview, float* dL_dproj, float* dL_dcampos, InputForm inf,
                            int cov_is_input /*cov3D is the caller's tensor (in its form), not the stored one*/,
-                           hipStream_t s);
+                           const float* opacities /*the forward's [P] (read when anti-aliased)*/,
+                           const uint32_t* mode_word /*the forward's GGR_CTR_ANTIALIAS word (device)*/, hipStream_t s);
 
 void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,
                          hipStream_t s);

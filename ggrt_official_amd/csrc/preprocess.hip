@@ -102,7 +102,10 @@ __device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, flo
 // JAC: also leave the Jacobian ∂colour/∂direction of every visible Gaussian (ggr_common.h sh_jac) for the backward — nine
 // more sums over the coefficients the colour evaluation has in LDS anyway, and 48 B written per Gaussian, against the
 // backward re-reading the whole SH row (192 / 300 B per Gaussian) for its view-direction term.
-template <bool MULTI, int KC, int PART, bool JAC>
+// AA: anti-aliasing (GgrForwardOptions.antialiasing) — the opacity scaled for the dilation (below).  A template parameter, not a
+// run-time branch: the AA = false kernels are the kernels without the feature, register for register (a uniform branch moved
+// their allocation by 2 VGPRs and one of them to another occupancy).  The colour half (PART = COLOUR) does not depend on it.
+template <bool MULTI, int KC, int PART, bool JAC, bool AA = false>
 __global__ void __launch_bounds__(GGR_PRE_THREADS)
 preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
                       const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -127,6 +130,10 @@ preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
         for (uint32_t wz = (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; wz < zero_words2;
              wz += gridDim.x * gridDim.y * blockDim.x)
             zero_area2[wz] = 0u;
+        // the mode the backward must differentiate (ggr_common.h GGR_CTR_ANTIALIAS): zero_area STARTS at that word, so every
+        // forward clears it above — in the thread that writes it here, after the clearing, when the frame is anti-aliased.
+        // (A store in every kernel, even of 0, moved the register allocation of default kernels by 1-2 VGPRs.)
+        if (AA && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) zero_area[0] = 1u;
     }
     // ---- Gaussian set blockIdx.y of the launch set (ViewSet.sets; one set: nothing moves) ----------------------------
     // The set's inputs are rows [set·P, (set+1)·P) of the caller's arrays, its views are views [v0, v0 + vps): every
@@ -256,6 +263,7 @@ preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
         // ---- geometry: visible (in front of the near plane, invertible 2D covariance, touches a tile) or culled ----
         bool vis = PART == GGR_PRE_COLOUR && in_range && rad_seen > 0;
         float px = 0.f, py = 0.f, con0 = 0.f, con1 = 0.f, con2 = 0.f;
+        float opac_out = opac;   // the splat record's opacity (anti-aliasing: scaled, below)
         float t0 = V[0] * p0 + V[4] * p1 + V[8] * p2 + V[12];
         float t1 = V[1] * p0 + V[5] * p1 + V[9] * p2 + V[13];
         const float t2 = V[2] * p0 + V[6] * p1 + V[10] * p2 + V[14];
@@ -295,6 +303,11 @@ preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
             const float a = c00 + GGR_DILATION, b = c01, c = c11 + GGR_DILATION;
             const float det = a * c - b * b;
             if (det != 0.0f) {
+                // ANTI-ALIASING (GgrForwardOptions.antialiasing; Mip-Splatting's 2D filter, upstream's `antialiasing`): the
+                // opacity is scaled by how much the dilation grew the footprint, sqrt(det(Σ) / det(Σ + 0.3·I)), clamped below.
+                // Everything after this point — the record's opacity, qmax, the tight rect — takes the scaled value.
+                float opac_e = opac;
+                if (AA) opac_e = opac * sqrtf(fmaxf(GGR_AA_MIN_RATIO, (c00 * c11 - b * b) / det));
                 const float det_inv = 1.f / det;
                 con0 = c * det_inv; con1 = -b * det_inv; con2 = a * det_inv;
                 const float mid = 0.5f * (a + c);
@@ -307,7 +320,9 @@ preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                 // oracle/ggr_oracle.c): a Gaussian whose projected geometry or opacity is not finite — or whose radius would
                 // overflow the int — takes no part in the frame.  (area stays 0: culled like an off-screen one.)
                 const bool finite = isfinite(px) && isfinite(py) && isfinite(con0) && isfinite(con1) && isfinite(con2) &&
-                                    isfinite(opac) && isfinite(a) && isfinite(c) && isfinite(t2) && radf < 1073741824.f;
+                                    isfinite(opac) && isfinite(opac_e) && isfinite(a) && isfinite(c) && isfinite(t2) &&
+                                    radf < 1073741824.f;
+                opac_out = opac_e;
                 const int rad = finite ? (int)radf : 0;
                 // (the reference clips the rect to the tile grid [0, gx] × [0, gy]; the scissor extension to its window's
                 //  tiles — the whole grid unless GgrSettings.scissor is set)
@@ -321,7 +336,7 @@ preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                     rad_out = rad;
                     int tx0 = rminx, ty0 = rminy, tx1 = rmaxx, ty1 = rmaxy;
                     if (inf.tight_rects) {   // ggr_common.h ggr_qmax_upper: tiles the α ≥ 1/255 ellipse cannot reach are dropped
-                        const float qmax = ggr_qmax_upper(opac);
+                        const float qmax = ggr_qmax_upper(opac_e);
                         if (qmax < 0.f) { tx1 = tx0; ty1 = ty0; }
                         else {
                             const float hx = sqrtf(qmax * a) * 1.01f + 0.5f, hy = sqrtf(qmax * c) * 1.01f + 0.5f;
@@ -473,7 +488,7 @@ preprocess_fwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
             float feat = t2;
             if (aux_precomp) feat = aux_in;
             else if (inf.aux_affine) feat = fmaxf(inf.aux_a + inf.aux_b * (t2 / in_s), 0.f);
-            s1 = make_float4(con2, opac, feat, 2.f * logf(255.f * opac));  // .w = qmax for the box cull
+            s1 = make_float4(con2, opac_out, feat, 2.f * logf(255.f * opac_out));  // .w = qmax for the box cull
             s2 = make_float4(rgb[0], rgb[1], rgb[2], 0.f);
         }
         if (in_range) {
@@ -526,7 +541,10 @@ void launch_preprocess_fwd(int P, int D, int M, const float* means3D, const floa
     // (sort_area_untouched: no depth sort will read the area — unless the per-tile sort has to be given up, and then the
     //  host clears it — so it is not cleared here: 9 MB of stores at C3; the block maxima are left where the sort expects them)
     const uint32_t sort_words = (uint32_t)ggr_sort_zero_words((size_t)P * vs.V, ggr_sort_segments((size_t)vs.V));
-    const uint32_t zero_words = sort_area_untouched ? 0u : sort_words;
+    // (cleared from the counters' GGR_CTR_ANTIALIAS word on: the mode word, the unused counters behind it, then the sort's
+    //  work area, which directly follows the counters — ggr_carve_geom)
+    uint32_t* const zero_from = g.counters + GGR_CTR_ANTIALIAS;
+    const uint32_t zero_words = (uint32_t)(g.hist - zero_from) + (sort_area_untouched ? 0u : sort_words);
     const int threads = GGR_PRE_THREADS;
     const int chunks = (P + threads - 1) / threads;
     // (colour_grid > 0, COLOUR only: that many persistent blocks walk the chunks — see the kernel)
@@ -541,12 +559,18 @@ void launch_preprocess_fwd(int P, int D, int M, const float* means3D, const floa
     const int kc = (shs && vs.vps == 1 && (deg == 3 || deg == 4)) ? (deg + 1) * (deg + 1) : 0;
     const size_t lds = (!shs || part == GGR_PRE_GEOMETRY) ? 0 : kc ? (size_t)threads * (kc | 1) * sizeof(float)
                                                                    : (size_t)threads * row_stride * sizeof(float);
-#define GGR_LAUNCH_PFWD_J(MULTI_, KC_, PART_, JAC_)                                                                       \
-    hipLaunchKernelGGL((preprocess_fwd_kernel<MULTI_, KC_, PART_, JAC_>), dim3(blocks, vs.sets), dim3(threads), lds, s, P, D, \
+#define GGR_LAUNCH_PFWD_A(MULTI_, KC_, PART_, JAC_, AA_)                                                                  \
+    hipLaunchKernelGGL((preprocess_fwd_kernel<MULTI_, KC_, PART_, JAC_, AA_>), dim3(blocks, vs.sets), dim3(threads), lds, s, P, D, \
                        M, means3D, shs, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp,       \
                        aux_precomp, vs, W, H, radii, g.splat, g.colour, g.sh_jac, (size_t)P * vs.V, g.keys_a, g.rect, g.clamped, g.cov3D,    \
-                       g.hist, zero_words, zero_area2, zero_words2, g.hist + sort_words,                                  \
+                       zero_from, zero_words, zero_area2, zero_words2, g.hist + sort_words,                               \
                        g.hist + ggr_sort_block_min_at((size_t)P * vs.V, ggr_sort_segments((size_t)vs.V)), inf)
+    // (AA: only the parts that write the splat record / the rects have an anti-aliased form; COLOUR is the same kernel)
+#define GGR_LAUNCH_PFWD_J(MULTI_, KC_, PART_, JAC_)                                                                       \
+    do {                                                                                                                  \
+        if (PART_ != GGR_PRE_COLOUR && inf.antialiasing) GGR_LAUNCH_PFWD_A(MULTI_, KC_, PART_, JAC_, PART_ != GGR_PRE_COLOUR); \
+        else GGR_LAUNCH_PFWD_A(MULTI_, KC_, PART_, JAC_, false);                                                          \
+    } while (0)
     const bool jac = keep_jacobian != 0 && shs != nullptr;
 #define GGR_LAUNCH_PFWD(MULTI_, KC_, PART_)                                                                               \
     do { if (jac) GGR_LAUNCH_PFWD_J(MULTI_, KC_, PART_, true); else GGR_LAUNCH_PFWD_J(MULTI_, KC_, PART_, false); } while (0)
@@ -564,6 +588,7 @@ void launch_preprocess_fwd(int P, int D, int M, const float* means3D, const floa
         else if (kc == 25) GGR_LAUNCH_PFWD(false, 25, GGR_PRE_ALL);
         else GGR_LAUNCH_PFWD(false, 0, GGR_PRE_ALL);
     }
+#undef GGR_LAUNCH_PFWD_A
 #undef GGR_LAUNCH_PFWD_J
 #undef GGR_LAUNCH_PFWD
 }

@@ -84,9 +84,12 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       float* __restrict__ dL_dopacity, float* __restrict__ dL_dsh, float* __restrict__ dL_dcolors_precomp,
                       float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscales,
                       float* __restrict__ dL_drotations, float* __restrict__ dL_daux,
-                      float* __restrict__ pose_acc, InputForm inf, int cov_is_input) {
+                      float* __restrict__ pose_acc, InputForm inf, int cov_is_input,
+                      const float* __restrict__ opacities, const uint32_t* __restrict__ mode_word) {
     extern __shared__ __attribute__((aligned(16))) float sh_lds[];  // [256][sh_stride]: SH in, dL/dSH out
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    // the forward's anti-aliasing mode (ggr_common.h GGR_CTR_ANTIALIAS, in the geometry buffer): uniform
+    const bool aa = mode_word[0] != 0u;
     const bool in_range = i < P;
     const int NV = MULTI ? vs.vps : 1;
     // ---- Gaussian set blockIdx.y of the launch set (as in preprocess_fwd): inputs and gradients are rows
@@ -101,7 +104,7 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
         radii += st_off; clamped += st_off; grad2d += GGR_G2D_STRIDE * st_off; sh_jac += st_off;
         dL_dmeans2D += 3 * st_off;
         if (dL_daux) dL_daux += st_off;
-        dL_dmeans3D += 3 * in_off; dL_dopacity += in_off;
+        dL_dmeans3D += 3 * in_off; dL_dopacity += in_off; opacities += in_off;
         if (dL_dsh) dL_dsh += in_off * (size_t)M * 3;
         if (dL_dcolors_precomp) dL_dcolors_precomp += 3 * in_off;
         if (dL_dcov3D) dL_dcov3D += (size_t)(cov_is_input ? inf.cov_stride : 6) * in_off;
@@ -181,7 +184,7 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
         const float g_z = r2.y;
         if (in_range) {
             ggr_st(dL_dmeans2D + 3 * o, r0.w); ggr_st(dL_dmeans2D + 3 * o + 1, r1.x); ggr_st(dL_dmeans2D + 3 * o + 2, 0.f);
-            dop += r2.x;
+            if (!aa) dop += r2.x;   // (anti-aliased: dL/dopacity = Σ_views dL/dopacity_eff · s, below)
         }
         float V[16], PM[16];
 #pragma unroll
@@ -247,6 +250,22 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                 dL_da = denom2inv * (-c * c * dcon0 + 2.f * b * c * dcon1 + (denom - a * c) * dcon2);
                 dL_dc = denom2inv * (-a * a * dcon2 + 2.f * a * b * dcon1 + (denom - a * c) * dcon0);
                 dL_db = denom2inv * 2.f * (b * c * dcon0 - (denom + 2.f * b * b) * dcon1 + a * b * dcon2);
+                if (aa) {
+                    // ANTI-ALIASING (preprocess.hip): the record's opacity was opacity · s, s = sqrt(max(GGR_AA_MIN_RATIO, r)),
+                    // r = det0 / det1 = (x·y − z²) / ((x+w)(y+w) − z²) with x = c00, y = c11, z = b, w = GGR_DILATION — upstream's
+                    // formulas.  The blend's opacity gradient is w.r.t. opacity · s: dL/dopacity takes it times s, and
+                    // dL/d(a, b, c) its product with opacity · ∂s/∂(x, z, y) — chained on to cov3D, the mean and the camera below.
+                    const float g_op = r2.x, w = GGR_DILATION, c00 = a - w, c11 = c - w;
+                    const float ratio = (c00 * c11 - b * b) / denom;
+                    const float sc = sqrtf(fmaxf(GGR_AA_MIN_RATIO, ratio));
+                    dop += g_op * sc;
+                    if (ratio > GGR_AA_MIN_RATIO) {   // (clamped: s does not depend on the covariance)
+                        const float k = g_op * opacities[il] / (2.f * sc * denom * denom);
+                        dL_da += k * w * (w * c11 + c11 * c11 + b * b);
+                        dL_dc += k * w * (w * c00 + c00 * c00 + b * b);
+                        dL_db += k * (-2.f * w * b * (w + c00 + c11));
+                    }
+                }
                 dcv[0] = A0[0] * A0[0] * dL_da + A0[0] * A1[0] * dL_db + A1[0] * A1[0] * dL_dc;
                 dcv[3] = A0[1] * A0[1] * dL_da + A0[1] * A1[1] * dL_db + A1[1] * A1[1] * dL_dc;
                 dcv[5] = A0[2] * A0[2] * dL_da + A0[2] * A1[2] * dL_db + A1[2] * A1[2] * dL_dc;
@@ -790,7 +809,8 @@ void launch_preprocess_bwd(int P, int D, int M, const float* means3D, const floa
                            float* dL_dopacity, float* dL_dsh,
                            float* dL_dcolors_precomp, float* dL_dcov3D, float* dL_dscales,
                            float* dL_drotations, float* dL_daux, float* pose_acc, float* dL_dview, float* dL_dproj,
-                           float* dL_dcampos, InputForm inf, int cov_is_input, hipStream_t s) {
+                           float* dL_dcampos, InputForm inf, int cov_is_input, const float* opacities,
+                           const uint32_t* mode_word, hipStream_t s) {
     if (P <= 0) return;
     const int blocks = (P + 255) / 256;
     const int deg = ggr_sh_degree(D, (!has_colors_precomp && shs) ? M : 25, inf.sh_cap);
@@ -811,7 +831,7 @@ void launch_preprocess_bwd(int P, int D, int M, const float* means3D, const floa
     hipLaunchKernelGGL((preprocess_bwd_kernel<POSE_, MULTI_, KC_, CM_>), dim3(blocks, vs.sets), dim3(256), lds, s, P, D, M, means3D, shs, \
                        sh_jac, (size_t)P * vs.V, has_colors_precomp, scales, rotations, scale_modifier, cov3D, vs, W, H, radii, clamped, grad2d,     \
                        has_dz, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dsh, dL_dcolors_precomp, dL_dcov3D, dL_dscales,   \
-                       dL_drotations, dL_daux, pose_acc, inf, cov_is_input)
+                       dL_drotations, dL_daux, pose_acc, inf, cov_is_input, opacities, mode_word)
 #define GGR_LAUNCH_PBWD_P(POSE_)                                                                                         \
     do {                                                                                                                  \
         if (multi) GGR_LAUNCH_PBWD(POSE_, true, 0, false);                                                                \

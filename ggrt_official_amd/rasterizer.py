@@ -78,6 +78,10 @@ class GaussianRasterizationSettings(NamedTuple):
     #                         outside the sync-free mode; global otherwise (GGRt's 660-tile frames).  The global sort runs in
     #                         its BUCKET form where it can (ABI 11: one partition pass + every bucket sorted in LDS; falls
     #                         back inside the call); "global_3pass" keeps the three radix passes
+    antialiasing: bool = False  # upstream's setting of the same name (graphdeco, 2024): Mip-Splatting's 2D filter — each
+    #                         Gaussian's opacity is scaled by sqrt(det Σ2D / det(Σ2D + 0.3·I)), the growth the 0.3 px² dilation
+    #                         gave its footprint (include/ggr_raster.h GgrForwardOptions); differentiated in the backward.
+    #                         False: as before.  GGRt's checkpoints were trained without it
 
 
 class StageProfile:
@@ -199,6 +203,12 @@ def clear_list_hints() -> None:
 def _scissor_key(rs):
     sc = getattr(rs, "scissor", None)
     return tuple(int(v) for v in sc) if sc else None
+
+
+def _aa_key(aa: bool) -> tuple:
+    """The shape key's anti-aliasing part: anti-aliased frames of a shape have other (shorter) lists under tight rects, so they
+    keep their own size / sort history; the default mode's key is the one it always was."""
+    return ("antialiasing",) if aa else ()
 
 
 def _capacity_guess(key):
@@ -470,10 +480,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             if prof is not None:
                 fout.stage_ms = C.cast(prof.fwd, C.c_void_p)
                 prof.fwd_calls += 1
-            key = (dev.index, P, W, H, 1, _scissor_key(rs))
+            aa = bool(getattr(rs, "antialiasing", False))
+            opt = _lib.forward_options(aa)
+            key = (dev.index, P, W, H, 1, _scissor_key(rs)) + _aa_key(aa)
             _sort_choice(key, rs, st)
             _sort_no_buckets(key, st)
-            _forward_with_guess(lambda: lib.ggr_forward(C.byref(st), C.byref(fin), C.byref(fout), cb, None, stream),
+            _forward_with_guess(lambda: lib.ggr_forward_opt(C.byref(st), C.byref(opt), C.byref(fin), C.byref(fout), cb, None,
+                                                            stream),
                                 fout, holder, lib, dev, W, H, key, capacity, prof is not None)
             _sort_look(key, lib, fout, geom, P, stream)
             _sort_fell_back(key, fout)
@@ -652,11 +665,13 @@ class _RasterizeViews(torch.autograd.Function):
             if prof is not None:
                 fout.stage_ms = C.cast(prof.fwd, C.c_void_p)
                 prof.fwd_calls += 1
-            key = (dev.index, P, W, H, V, _scissor_key(rs))
+            aa = bool(getattr(rs, "antialiasing", False))
+            opt = _lib.forward_options(aa)
+            key = (dev.index, P, W, H, V, _scissor_key(rs)) + _aa_key(aa)
             _sort_choice(key, rs, st)
             _sort_no_buckets(key, st)
-            _forward_with_guess(lambda: lib.ggr_forward_views(C.byref(st), C.byref(vw), C.byref(fin), C.byref(fout), cb,
-                                                              None, stream),
+            _forward_with_guess(lambda: lib.ggr_forward_views_opt(C.byref(st), C.byref(opt), C.byref(vw), C.byref(fin),
+                                                                  C.byref(fout), cb, None, stream),
                                 fout, holder, lib, dev, W, H, key, capacity, prof is not None)
             _sort_look(key, lib, fout, geom, P * V, stream)
             _sort_fell_back(key, fout)

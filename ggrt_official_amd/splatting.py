@@ -169,14 +169,18 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
 
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
-                       use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None):
+                       use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,
+                       antialiasing=False):
     """Everything ``render_cuda`` hands to the rasterizer, batched: a list of
     (GaussianRasterizationSettings, kwargs) per view.  Split out so the golden-vector tests can
     compare it with what the reference's call site produces.
 
     ``gaussian_covariances=None`` selects the fused-adapter form (§8f-4): ``gaussian_scales[b,g,3]`` +
     world-space ``gaussian_rotations[b,g,4]`` (w,x,y,z) go to the rasterizer's ``scales``/``rotations``
-    inputs; the scale-invariant renormalisation then multiplies the scales by 1/near (≡ cov × 1/near²)."""
+    inputs; the scale-invariant renormalisation then multiplies the scales by 1/near (≡ cov × 1/near²).
+
+    ``antialiasing=True``: upstream's anti-aliased rasterization (``GaussianRasterizationSettings.antialiasing``) — off by
+    default, as GGRt's checkpoints were trained."""
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
     fused_adapter = gaussian_covariances is None
     if fused_adapter and (gaussian_scales is None or gaussian_rotations is None):
@@ -211,7 +215,8 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
             image_height=h, image_width=w, tanfovx=tan_host[i][0], tanfovy=tan_host[i][1],
             bg=background_color[i], scale_modifier=1.0, viewmatrix=view[i], projmatrix=full[i],
             sh_degree=degree, campos=extrinsics[i, :3, 3], prefiltered=False,
-            sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}))
+            sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}),
+            **({"antialiasing": True} if antialiasing else {}))
         kwargs = dict(means3D=gaussian_means[i], shs=shs[i] if use_sh else None,
                       colors_precomp=None if use_sh else shs[i, :, 0, :],
                       opacities=gaussian_opacities[i, ..., None])
@@ -244,16 +249,18 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_means: Tensor, gaussian_covariances: Tensor, gaussian_sh_coefficients: Tensor,
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
-                scissor=None, sh_max_degree: Optional[int] = None) -> Tensor:
+                scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False) -> Tensor:
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
 
     ``scissor=(x0, y0, x1, y1)`` (extension): render only the tiles overlapping that pixel window — for the
     fine-tune loop's deferred back-propagation (``finetune_ggrt_stable.py:126-142``), which renders the whole frame
-    per crop cell and slices one cell out.  Inside the window the image equals the full render bit for bit."""
+    per crop cell and slices one cell out.  Inside the window the image equals the full render bit for bit.
+
+    ``antialiasing=True`` (upstream's setting): opacities compensated for the screen-space dilation (``boundary_arguments``)."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
-                               use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree)
+                               use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing)
     return torch.stack([o[0] for o in _rasterize_views(calls)])
 
 
@@ -278,14 +285,14 @@ def depth_feature(extrinsics: Tensor, gaussian_means: Tensor, near: Tensor, far:
 
 def render_depth_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape,
                       gaussian_means: Tensor, gaussian_covariances: Tensor, gaussian_opacities: Tensor,
-                      scale_invariant: bool = True, mode: DepthRenderingMode = "depth") -> Tensor:
+                      scale_invariant: bool = True, mode: DepthRenderingMode = "depth", antialiasing: bool = False) -> Tensor:
     """Depth as colour, black background, channel mean → [batch,h,w] (reference ``cuda_splatting.py:227-269``)."""
     fake_color = depth_feature(extrinsics, gaussian_means, near, far, mode)
     b = fake_color.shape[0]
     result = render_cuda(extrinsics, intrinsics, near, far, image_shape,
                          torch.zeros((b, 3), dtype=fake_color.dtype, device=fake_color.device), gaussian_means,
                          gaussian_covariances, fake_color[:, :, None, None].expand(-1, -1, 3, 1), gaussian_opacities,
-                         scale_invariant=scale_invariant)
+                         scale_invariant=scale_invariant, antialiasing=antialiasing)
     return result.mean(dim=1)
 
 
@@ -297,7 +304,8 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            gaussian_sh_coefficients: Tensor, gaussian_opacities: Tensor,
                            depth_mode: DepthRenderingMode = "depth", scale_invariant: bool = True,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
-                           gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None):
+                           gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
+                           antialiasing: bool = False):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
 
@@ -310,7 +318,7 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     aux = (0.5 + SH_C0 * feat).clamp(min=0.0)
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
-                               use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree)
+                               use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing)
     outs = _rasterize_views(calls, aux=aux)
     return torch.stack([o[0] for o in outs]), torch.stack([o[2] for o in outs])
 
@@ -319,7 +327,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                        background_color: Tensor, gaussians: Gaussians, view_to_batch,
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
-                       sh_max_degree: Optional[int] = None):
+                       sh_max_degree: Optional[int] = None, antialiasing: bool = False):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
     * ``device_camera``: view / projection matrices, camera position, tan(fov/2) and 1/near of all views come
@@ -391,7 +399,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             image_height=h, image_width=w, tanfovx=0.0, tanfovy=0.0, bg=background_color[0], scale_modifier=1.0,
             viewmatrix=view[0], projmatrix=full[0], sh_degree=degree, campos=campos[0], prefiltered=False,
             list_capacity=list_capacity * n, sh_channel_major=True, aux_affine=aux_affine,
-            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor))
+            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing))
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
         col, _, dep = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
@@ -433,7 +441,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             image_height=h, image_width=w, tanfovx=0.0, tanfovy=0.0, bg=background_color[idx[0]], scale_modifier=1.0,
             viewmatrix=view[idx[0]], projmatrix=full[idx[0]], sh_degree=degree, campos=campos[idx[0]],
             prefiltered=False, list_capacity=list_capacity * len(idx), sh_channel_major=True, aux_affine=aux_affine,
-            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor))
+            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing))
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         col, _, dep = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
                                       take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
@@ -457,7 +465,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             campos=campos[i], prefiltered=False, list_capacity=list_capacity,
             input_scale=None if scale is None else scale[i:i + 1], sh_channel_major=True, aux_affine=aux_affine,
             tanfov=None if tanfov is None else tanfov[i], sh_max_degree=sh_cap,
-            scissor=None if scissor is None else tuple(scissor))
+            scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing))
         means = g_means[b]
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
@@ -477,9 +485,12 @@ class DecoderSplattingCUDA(nn.Module):
     depth_mode) -> DecoderOutput(color[b,v,3,h,w], depth[b,v,h,w] | None)``."""
 
     def __init__(self, cfg=None, fused_depth: bool = True, fused_inputs: bool = True, list_capacity: int = 0,
-                 sh_max_degree: Optional[int] = None):
+                 sh_max_degree: Optional[int] = None, antialiasing: bool = False):
         super().__init__()
         self.cfg = cfg
+        # upstream's anti-aliased rasterization (GaussianRasterizationSettings.antialiasing) for every render of this decoder;
+        # False (default): as GGRt's checkpoints were trained (INTEGRATION.md §11)
+        self.antialiasing = bool(antialiasing)
         # 3 / 4: the explicit choice of INTEGRATION.md §7, for THIS decoder (two decoders of one process may differ); None =
         # this layer's default at the time of each call (set_sh_max_degree / GGR_SH_MAX_DEGREE)
         self.sh_max_degree = None if sh_max_degree is None else resolve_sh_max_degree(sh_max_degree)
@@ -520,7 +531,7 @@ class DecoderSplattingCUDA(nn.Module):
             color, depth = render_views_fused(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
-                scissor=scissor, sh_max_degree=self.sh_max_degree)
+                scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing)
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]),
                                  None if depth is None else depth.reshape(b, v, *depth.shape[1:]))
         if depth_mode is not None and self.fused_depth:
@@ -528,13 +539,13 @@ class DecoderSplattingCUDA(nn.Module):
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 self._per_view(gaussians.means, v), self._opt_per_view(gaussians.covariances, v),
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
-                sh_max_degree=self.sh_max_degree, **self._ellipsoids(gaussians, v))
+                sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, **self._ellipsoids(gaussians, v))
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]))
         color = render_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                             image_shape, bg, self._per_view(gaussians.means, v),
                             self._opt_per_view(gaussians.covariances, v), self._per_view(gaussians.harmonics, v),
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
-                            **self._ellipsoids(gaussians, v))
+                            antialiasing=self.antialiasing, **self._ellipsoids(gaussians, v))
         color = color.reshape(b, v, *color.shape[1:])
         depth = None if depth_mode is None else self.render_depth(gaussians, extrinsics, intrinsics, near, far,
                                                                   image_shape, depth_mode)
@@ -546,5 +557,5 @@ class DecoderSplattingCUDA(nn.Module):
         result = render_depth_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                                    image_shape, self._per_view(gaussians.means, v),
                                    self._per_view(gaussians.covariances, v), self._per_view(gaussians.opacities, v),
-                                   mode=mode)
+                                   mode=mode, antialiasing=self.antialiasing)
         return result.reshape(b, v, *result.shape[1:])

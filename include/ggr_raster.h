@@ -283,6 +283,29 @@ size_t ggr_backward_scratch_bytes(int32_t num_points);
 int ggr_forward(const GgrSettings* settings, const GgrForwardIn* in, GgrForwardOut* out,
                 GgrAllocFn alloc, void* alloc_ctx, void* stream);
 
+/* ---- forward options (ABI 11, additive: no struct of the calls above grows, no signature changes) ----------------------
+ * Later options are appended to this struct, not given new entry points: the library reads the fields `struct_size` covers.
+ *
+ * antialiasing = 1: upstream's `antialiasing` setting — the 2D Mip filter of Mip-Splatting (Yu et al., CVPR 2024).  The
+ * 0.3 px² screen-space dilation stays, and each Gaussian's opacity is scaled by how much it grew the footprint:
+ *     opacity_eff = opacity · sqrt(max(2.5e-5, det(Σ2D) / det(Σ2D + 0.3·I)))
+ * per view.  opacity_eff is what the pixels see (the blend's α, the α >= 1/255 culls, the tight tile rects); radius, conic,
+ * depth order and colour are those of antialiasing = 0.  Without it a splat smaller than a pixel is blown up to the
+ * dilation's size at full opacity and renders too bright and too thick below the resolution it was fitted at.  The backward
+ * differentiates the factor (w.r.t. opacity, means, covariance / scale / rotation and the camera); it needs no option of its
+ * own: the forward records the mode in the geometry buffer and ggr_backward / ggr_backward_views read it there on the device
+ * (no read-back: sync-free mode and graph capture are unaffected), so a backward always differentiates its forward's mode.
+ * Same constants as upstream.  The non-finite contract above holds unchanged. */
+typedef struct GgrForwardOptions {
+    int32_t struct_size;    /* sizeof(GgrForwardOptions): later options are appended, not given new entry points */
+    int32_t antialiasing;   /* 0: as ggr_forward.  1: opacity compensated for the dilation (above) */
+} GgrForwardOptions;
+
+/* ggr_forward with options; `options` NULL = ggr_forward.  A struct_size smaller than the two fields above, or an antialiasing
+ * value other than 0 / 1, returns GGR_E_INVALID before anything is enqueued. */
+int ggr_forward_opt(const GgrSettings* settings, const GgrForwardOptions* options, const GgrForwardIn* in,
+                    GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream);
+
 /* replaces diff_gaussian_rasterization._C.rasterize_gaussians_backward */
 int ggr_backward(const GgrSettings* settings, const GgrBackwardIn* in, GgrBackwardOut* out,
                  void* stream);
@@ -331,6 +354,10 @@ size_t ggr_backward_scratch_bytes_views(int32_t num_points, int32_t num_views);
  * buffers sized with the *_views queries; num_rendered counts the entries of all views. */
 int ggr_forward_views(const GgrSettings* settings, const GgrViews* views, const GgrForwardIn* in, GgrForwardOut* out,
                       GgrAllocFn alloc, void* alloc_ctx, void* stream);
+
+/* ggr_forward_views with options (GgrForwardOptions; NULL = ggr_forward_views) */
+int ggr_forward_views_opt(const GgrSettings* settings, const GgrForwardOptions* options, const GgrViews* views,
+                          const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream);
 
 /* As ggr_backward.  dL_dout_color [V,3,H,W], dL_dout_depth [V,H,W] or NULL, radii [V,P].  Gradients w.r.t. the
  * Gaussians come out SUMMED over the views ([P,…]); dL_dmeans2D and dL_daux are per view ([V,P,3], [V,P]); the camera
