@@ -8,7 +8,7 @@ highest SH band (`ggrt_official_amd.splatting.SH_MAX_DEGREE`: `set_sh_max_degree
 otherwise — INTEGRATION.md §7), silently, exactly as `ggrt_official_amd.splatting.render_cuda` does: the two documented
 integration paths render the same images.  (`ggrt_official_amd.GaussianRasterizer`, the raw rasterizer, keeps "not chosen
 = bands 0..3 with one warning".)  Upstream's `antialiasing=` keyword of the settings passes through unchanged (False by
-default, as upstream).  Nothing else lives here."""
+default, as upstream), and so does the `return_alpha=` extension (False: the 3-tuple).  Nothing else lives here."""
 from ggrt_official_amd import rasterizer as _r
 from ggrt_official_amd.rasterizer import GaussianRasterizationSettings  # noqa: F401
 

@@ -79,6 +79,24 @@ def forward_options(antialiasing: bool = False) -> GgrForwardOptions:
     return GgrForwardOptions(struct_size=C.sizeof(GgrForwardOptions), antialiasing=int(bool(antialiasing)))
 
 
+class GgrForwardExtra(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("out_alpha", C.c_void_p)]
+
+
+class GgrBackwardExtra(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("dL_dout_alpha", C.c_void_p)]
+
+
+def forward_extra(out_alpha=None) -> GgrForwardExtra:
+    """The extra planes of ggr_forward_ext / ggr_forward_views_ext (include/ggr_raster.h), struct_size filled in."""
+    return GgrForwardExtra(struct_size=C.sizeof(GgrForwardExtra), reserved=0, out_alpha=out_alpha)
+
+
+def backward_extra(dL_dout_alpha=None) -> GgrBackwardExtra:
+    """The extra planes of ggr_backward_ext / ggr_backward_views_ext, struct_size filled in."""
+    return GgrBackwardExtra(struct_size=C.sizeof(GgrBackwardExtra), reserved=0, dL_dout_alpha=dL_dout_alpha)
+
+
 FWD_STAGES = ["preprocess", "depth_sort", "tile_count", "tile_scatter", "blend", "colour_side_stream", "tile_sort"]
 DEPTH_SORT = {"auto": 0, "global": 1, "per_tile": 2, "global_3pass": 0x101}
 DEPTH_SORT_NO_BUCKETS = 0x100      # IN flag: never the global sort's bucket form (include/ggr_raster.h)
@@ -118,6 +136,15 @@ SYMBOLS = [
     ("ggr_forward_views_opt", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrForwardOptions), C.POINTER(GgrViews),
                                         C.POINTER(GgrForwardIn), C.POINTER(GgrForwardOut), ALLOC_FN, C.c_void_p,
                                         C.c_void_p]),
+    ("ggr_forward_ext", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrForwardOptions), C.POINTER(GgrForwardExtra),
+                                  C.POINTER(GgrForwardIn), C.POINTER(GgrForwardOut), ALLOC_FN, C.c_void_p, C.c_void_p]),
+    ("ggr_backward_ext", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrBackwardExtra), C.POINTER(GgrBackwardIn),
+                                   C.POINTER(GgrBackwardOut), C.c_void_p]),
+    ("ggr_forward_views_ext", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrForwardOptions), C.POINTER(GgrForwardExtra),
+                                        C.POINTER(GgrViews), C.POINTER(GgrForwardIn), C.POINTER(GgrForwardOut), ALLOC_FN,
+                                        C.c_void_p, C.c_void_p]),
+    ("ggr_backward_views_ext", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrBackwardExtra), C.POINTER(GgrViews),
+                                         C.POINTER(GgrBackwardIn), C.POINTER(GgrBackwardOut), C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),

@@ -86,6 +86,17 @@ int validate_options(const GgrForwardOptions* opt, int* antialiasing) {
     return GGR_OK;
 }
 
+// GgrForwardExtra / GgrBackwardExtra: NULL = no extra plane; checked before anything is enqueued
+template <typename E>
+int validate_extra(const E* ex, const char* name) {
+    if (!ex) return GGR_OK;
+    if (ex->struct_size < (int32_t)sizeof(E))
+        return fail(GGR_E_INVALID, "%s.struct_size %d is smaller than the %d bytes of its fields", name, (int)ex->struct_size,
+                    (int)sizeof(E));
+    if (ex->reserved != 0) return fail(GGR_E_INVALID, "%s.reserved must be 0, not %d", name, (int)ex->reserved);
+    return GGR_OK;
+}
+
 int validate(const GgrSettings* st, const GgrForwardIn* in) {
     if (!st || !in) return fail(GGR_E_INVALID, "null settings / inputs");
     if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0)
@@ -474,7 +485,7 @@ namespace {
 // the tiles of the views are stacked (ggr_common.h ViewSet): one preprocess launch, ONE depth sort over the V·P keys,
 // one tile-list build over the V·T tiles, one blend launch.
 int forward_impl(const GgrSettings* st, const ViewSet& vs, const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc,
-                 void* alloc_ctx, void* stream, int antialiasing) {
+                 void* alloc_ctx, void* stream, int antialiasing, float* out_alpha) {
     if (!out || !out->out_color || !out->geom_buffer || !out->image_buffer || !alloc)
         return fail(GGR_E_INVALID, "null output / buffer / allocator");
     if (st->num_points > 0 && !out->radii) return fail(GGR_E_INVALID, "null radii");
@@ -666,7 +677,7 @@ int forward_impl(const GgrSettings* st, const ViewSet& vs, const GgrForwardIn* i
         if (colour_pending) (void)fork_colour();   // (a frame without list entries: nothing started it yet)
         joiner.join();   // the colour records (side stream) are complete before the blend reads them
         ggr::launch_blend_fwd(W, H, im.ranges, point_list, g.splat, g.colour, vs.bg, out->out_color, out->no_backward ? nullptr : im.final_T,
-                              im.n_contrib, out->out_depth, out->no_backward ? nullptr : im.ckpt, im.ckpt_slots, im.tile_top, NV,
+                              im.n_contrib, out->out_depth, out_alpha, out->no_backward ? nullptr : im.ckpt, im.ckpt_slots, im.tile_top, NV,
                               scissored ? 1 : 0, out->backward_scratch, ggr_carve_bwd(nullptr, (size_t)P1, (size_t)NV).bytes, s);
     };
     // what the host word(s) said: N, or a fault; the longest list
@@ -832,7 +843,8 @@ int forward_impl(const GgrSettings* st, const ViewSet& vs, const GgrForwardIn* i
     return GGR_OK;
 }
 
-int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn* in, GgrBackwardOut* out, void* stream) {
+int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn* in, GgrBackwardOut* out, void* stream,
+                  const float* dL_dalpha) {
     if (!out) return fail(GGR_E_INVALID, "null gradient output struct");
     const int NV = vs.V;
     if (st->num_points == 0) {  // nothing to differentiate; camera gradients are zero
@@ -870,7 +882,7 @@ int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn*
 
     if (in->num_rendered != 0) {  // (-1: sync-free forward, count known on the device only)
         ggr::launch_blend_bwd(W, H, im.ranges, point_list, g.splat, g.colour, vs.bg, im.final_T, im.n_contrib,
-                              in->dL_dout_color, in->dL_dout_depth, sc.grad2d, im.tile_top, im.ckpt,
+                              in->dL_dout_color, in->dL_dout_depth, dL_dalpha, sc.grad2d, im.tile_top, im.ckpt,
                               im.ckpt_slots, im.bwd_segments, NV, s);
         KCHECK(dbg, s, "blend_bwd");
     }
@@ -893,57 +905,83 @@ int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn*
 
 extern "C" {
 
-int ggr_forward_opt(const GgrSettings* st, const GgrForwardOptions* opt, const GgrForwardIn* in, GgrForwardOut* out,
-                    GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+int ggr_forward_ext(const GgrSettings* st, const GgrForwardOptions* opt, const GgrForwardExtra* ex, const GgrForwardIn* in,
+                    GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream) {
     g_err[0] = 0;
     int aa = 0;
     int rc = validate_options(opt, &aa);
     if (rc) return rc;
+    if ((rc = validate_extra(ex, "GgrForwardExtra")) != 0) return rc;
     rc = validate(st, in);
     if (rc) return rc;
-    return forward_impl(st, single_view(st, in), in, out, alloc, alloc_ctx, stream, aa);
+    return forward_impl(st, single_view(st, in), in, out, alloc, alloc_ctx, stream, aa, ex ? ex->out_alpha : nullptr);
+}
+
+int ggr_forward_opt(const GgrSettings* st, const GgrForwardOptions* opt, const GgrForwardIn* in, GgrForwardOut* out,
+                    GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+    return ggr_forward_ext(st, opt, nullptr, in, out, alloc, alloc_ctx, stream);
 }
 
 int ggr_forward(const GgrSettings* st, const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc,
                 void* alloc_ctx, void* stream) {
-    return ggr_forward_opt(st, nullptr, in, out, alloc, alloc_ctx, stream);
+    return ggr_forward_ext(st, nullptr, nullptr, in, out, alloc, alloc_ctx, stream);
+}
+
+int ggr_backward_ext(const GgrSettings* st, const GgrBackwardExtra* ex, const GgrBackwardIn* in, GgrBackwardOut* out,
+                     void* stream) {
+    g_err[0] = 0;
+    int rc = validate_extra(ex, "GgrBackwardExtra");
+    if (rc) return rc;
+    if (!in) return fail(GGR_E_INVALID, "null inputs");
+    rc = validate(st, &in->fwd);
+    if (rc) return rc;
+    return backward_impl(st, single_view(st, &in->fwd), in, out, stream, ex ? ex->dL_dout_alpha : nullptr);
 }
 
 int ggr_backward(const GgrSettings* st, const GgrBackwardIn* in, GgrBackwardOut* out, void* stream) {
-    g_err[0] = 0;
-    if (!in) return fail(GGR_E_INVALID, "null inputs");
-    int rc = validate(st, &in->fwd);
-    if (rc) return rc;
-    return backward_impl(st, single_view(st, &in->fwd), in, out, stream);
+    return ggr_backward_ext(st, nullptr, in, out, stream);
 }
 
-int ggr_forward_views_opt(const GgrSettings* st, const GgrForwardOptions* opt, const GgrViews* views, const GgrForwardIn* in,
-                          GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+int ggr_forward_views_ext(const GgrSettings* st, const GgrForwardOptions* opt, const GgrForwardExtra* ex, const GgrViews* views,
+                          const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream) {
     g_err[0] = 0;
     int aa = 0;
     int rc = validate_options(opt, &aa);
     if (rc) return rc;
+    if ((rc = validate_extra(ex, "GgrForwardExtra")) != 0) return rc;
     rc = validate(st, in);
     if (rc) return rc;
     ViewSet vs;
     if ((rc = view_set(st, views, &vs)) != 0) return rc;
-    return forward_impl(st, vs, in, out, alloc, alloc_ctx, stream, aa);
+    return forward_impl(st, vs, in, out, alloc, alloc_ctx, stream, aa, ex ? ex->out_alpha : nullptr);
+}
+
+int ggr_forward_views_opt(const GgrSettings* st, const GgrForwardOptions* opt, const GgrViews* views, const GgrForwardIn* in,
+                          GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream) {
+    return ggr_forward_views_ext(st, opt, nullptr, views, in, out, alloc, alloc_ctx, stream);
 }
 
 int ggr_forward_views(const GgrSettings* st, const GgrViews* views, const GgrForwardIn* in, GgrForwardOut* out,
                       GgrAllocFn alloc, void* alloc_ctx, void* stream) {
-    return ggr_forward_views_opt(st, nullptr, views, in, out, alloc, alloc_ctx, stream);
+    return ggr_forward_views_ext(st, nullptr, nullptr, views, in, out, alloc, alloc_ctx, stream);
+}
+
+int ggr_backward_views_ext(const GgrSettings* st, const GgrBackwardExtra* ex, const GgrViews* views, const GgrBackwardIn* in,
+                           GgrBackwardOut* out, void* stream) {
+    g_err[0] = 0;
+    int rc = validate_extra(ex, "GgrBackwardExtra");
+    if (rc) return rc;
+    if (!in) return fail(GGR_E_INVALID, "null inputs");
+    rc = validate(st, &in->fwd);
+    if (rc) return rc;
+    ViewSet vs;
+    if ((rc = view_set(st, views, &vs)) != 0) return rc;
+    return backward_impl(st, vs, in, out, stream, ex ? ex->dL_dout_alpha : nullptr);
 }
 
 int ggr_backward_views(const GgrSettings* st, const GgrViews* views, const GgrBackwardIn* in, GgrBackwardOut* out,
                        void* stream) {
-    g_err[0] = 0;
-    if (!in) return fail(GGR_E_INVALID, "null inputs");
-    int rc = validate(st, &in->fwd);
-    if (rc) return rc;
-    ViewSet vs;
-    if ((rc = view_set(st, views, &vs)) != 0) return rc;
-    return backward_impl(st, vs, in, out, stream);
+    return ggr_backward_views_ext(st, nullptr, views, in, out, stream);
 }
 
 size_t ggr_geom_bytes_inference(int32_t P, int32_t V) {

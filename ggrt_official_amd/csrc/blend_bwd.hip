@@ -112,15 +112,18 @@ __device__ __forceinline__ float transpose_cols8(const float (&o)[8], int lane) 
     return keep + dpp_mov<0x141>(send);       // row_half_mirror
 }
 
+// HAS_ALPHA (GgrBackwardExtra.dL_dout_alpha): a gradient w.r.t. the accumulated opacity 1 − T_final.  d(1 − T_final)/dα_s =
+// T_final/(1 − α_s), which is the background term of the colour with −dL/dalpha in place of bg·dL/dpixel: only the seed of R
+// changes.  An instance of its own, launched only on request: the default instances keep their resources.
 // [budget: prologue]
-template <bool HAS_DEPTH>
+template <bool HAS_DEPTH, bool HAS_ALPHA>
 __global__ void __launch_bounds__(256)
 blend_bwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
                  const uint32_t* __restrict__ point_list, const float4* __restrict__ splat,
                  const float4* __restrict__ colour,
                  const float* __restrict__ bg, const float* __restrict__ final_T,
                  const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-                 const float* __restrict__ dL_ddepth, float* __restrict__ grad2d,
+                 const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha, float* __restrict__ grad2d,
                  const uint32_t* __restrict__ tile_top, const float* __restrict__ ckpt, int ckpt_slots,
                  int segments, int views) {
     __shared__ StagedSplat stage[BATCH];
@@ -168,15 +171,17 @@ blend_bwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
         const size_t vo = (size_t)view * hw;
         final_T += vo; n_contrib += vo; dL_dpix += 3 * vo; bg += 3 * view;
         if (HAS_DEPTH) dL_ddepth += vo;
+        if (HAS_ALPHA) dL_dalpha += vo;
         if (ckpt) ckpt += (size_t)ckpt_slots * GGR_CKPT_FLOATS * vo;
     }
 
     const float T_final = inside ? final_T[pid] : 0.f;
     uint32_t last = inside ? n_contrib[pid] : 0u;
-    float dp0 = 0.f, dp1 = 0.f, dp2 = 0.f, dpz = 0.f;
+    float dp0 = 0.f, dp1 = 0.f, dp2 = 0.f, dpz = 0.f, dpa = 0.f;
     if (inside) {
         dp0 = dL_dpix[pid]; dp1 = dL_dpix[hw + pid]; dp2 = dL_dpix[2 * hw + pid];
         if (HAS_DEPTH) dpz = dL_ddepth[pid];
+        if (HAS_ALPHA) dpa = dL_dalpha[pid];
     }
     // ---- zero-gradient window skip ------------------------------------------------------------------------------
     // A pixel whose upstream gradient is exactly zero contributes exactly zero to every sum below (each term is a
@@ -184,7 +189,8 @@ blend_bwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
     // back-propagates, per crop cell, a gradient that is zero outside the cell through a full-frame render
     // (finetune_ggrt_stable.py:126-142): a wave whose quadrant carries no gradient then has no survivors, and a
     // workgroup whose 256 pixels carry none — or whose live pixels all end before this depth segment — leaves below.
-    if (dp0 == 0.f && dp1 == 0.f && dp2 == 0.f && dpz == 0.f) last = 0u;
+    // (a pixel that carries only an alpha gradient is live: its entries have nonzero dL/dα through R)
+    if (dp0 == 0.f && dp1 == 0.f && dp2 == 0.f && dpz == 0.f && (!HAS_ALPHA || dpa == 0.f)) last = 0u;
     const float bg_dot = bg[0] * dp0 + bg[1] * dp1 + bg[2] * dp2;
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
 
@@ -200,7 +206,9 @@ blend_bwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
     if (seg_lo >= seg_hi) return;  // (block-uniform; no barrier is pending)
 
     float T = T_final;
-    float R = T_final * bg_dot;  // everything behind the current entry, dotted with dL/dpixel (see the slot body)
+    // everything behind the current entry, dotted with dL/dpixel (see the slot body); with an alpha gradient the background
+    // term T_final·(bg·dL/dpixel) becomes T_final·(bg·dL/dpixel − dL/dalpha)
+    float R = T_final * (HAS_ALPHA ? bg_dot - dpa : bg_dot);
     // (scalar register operands instead of 32-bit literals in every v_min / v_cmp of the slot body: a literal costs 2 more
     //  issue cycles per instruction — tools/valu_peak_bench.hip; scripts/valu_budget.py: 12 literal instructions per trip)
     float amax = GGR_ALPHA_MAX, amin = GGR_ALPHA_MIN;
@@ -425,21 +433,25 @@ blend_bwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
 void launch_blend_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const float4* splat,
                       const float4* colour,
                       const float* bg, const float* final_T, const uint32_t* n_contrib,
-                      const float* dL_dpix, const float* dL_ddepth, float* grad2d, const uint32_t* tile_top,
-                      const float* ckpt, int ckpt_slots, int segments, int views, hipStream_t s) {
+                      const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* grad2d,
+                      const uint32_t* tile_top, const float* ckpt, int ckpt_slots, int segments, int views, hipStream_t s) {
     const int gx = (W + GGR_TILE - 1) / GGR_TILE, gy = (H + GGR_TILE - 1) / GGR_TILE;
     if (gx * gy * views == 0) return;
     const int nt = gx * gy * views;
     // one workgroup per (checkpoint interval, tile): `segments` == the forward's slot count, or 1 without checkpoints
     segments = (ckpt && ckpt_slots >= 2) ? ckpt_slots : 1;
-    if (dL_ddepth)
-        hipLaunchKernelGGL(blend_bwd_kernel<true>, dim3(xcd_grid(nt) * segments), dim3(256), 0, s, W, H, gx, ranges,
-                           point_list, splat, colour, bg, final_T, n_contrib, dL_dpix, dL_ddepth, grad2d, tile_top, ckpt,
-                           ckpt_slots, segments, views);
-    else
-        hipLaunchKernelGGL(blend_bwd_kernel<false>, dim3(xcd_grid(nt) * segments), dim3(256), 0, s, W, H, gx, ranges,
-                           point_list, splat, colour, bg, final_T, n_contrib, dL_dpix, dL_ddepth, grad2d, tile_top, ckpt,
-                           ckpt_slots, segments, views);
+#define GGR_LAUNCH_BBWD(DEPTH_, ALPHA_)                                                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(blend_bwd_kernel<DEPTH_, ALPHA_>), dim3(xcd_grid(nt) * segments), dim3(256), 0, s, W, H, gx,  \
+                       ranges, point_list, splat, colour, bg, final_T, n_contrib, dL_dpix, dL_ddepth, dL_dalpha, grad2d,       \
+                       tile_top, ckpt, ckpt_slots, segments, views)
+    if (dL_dalpha) {
+        if (dL_ddepth) GGR_LAUNCH_BBWD(true, true);
+        else GGR_LAUNCH_BBWD(false, true);
+    } else {
+        if (dL_ddepth) GGR_LAUNCH_BBWD(true, false);
+        else GGR_LAUNCH_BBWD(false, false);
+    }
+#undef GGR_LAUNCH_BBWD
 }
 
 }  // namespace ggr

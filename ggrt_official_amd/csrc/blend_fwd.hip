@@ -35,14 +35,18 @@ void blend_fwd_counters(unsigned long long* out, int reset) {
 
 // TRAIN = false (GgrForwardOut.no_backward: inference, torch.no_grad()): nothing is kept for a backward — no last contributor
 // per pixel (one select per survivor in a loop bound by vector issue: 150.6 → 142.0 µs at C3), no final T; tile_top = 0.
+// ALPHA (GgrForwardExtra.out_alpha): the accumulated opacity 1 − T of every pixel is written beside the colour — T is the
+// transmittance the colour multiplies bg by, so a pixel without contributors gets 0.  An instance of its own, launched only
+// on request: the default instances keep their resources.
 // [budget: prologue]  (scripts/valu_budget.py)
-template <bool TRAIN>
+template <bool TRAIN, bool ALPHA>
 __global__ void __launch_bounds__(256)
 blend_fwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
                  const uint32_t* __restrict__ point_list, const float4* __restrict__ splat,
                  const float4* __restrict__ colour,
                  const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ final_T,
-                 uint32_t* __restrict__ n_contrib, float* __restrict__ out_depth, float* __restrict__ ckpt,
+                 uint32_t* __restrict__ n_contrib, float* __restrict__ out_depth, float* __restrict__ out_alpha,
+                 float* __restrict__ ckpt,
                  int ckpt_slots, uint32_t* __restrict__ tile_top, int views, int interleaved, float4* __restrict__ zero4,
                  size_t zero4_n) {
     __shared__ StagedSplat stage[BATCH + 1];   // + the null record that pads a wave's survivor list
@@ -87,6 +91,7 @@ blend_fwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
         out_color += 3 * vo; n_contrib += vo; bg += 3 * view;
         if (TRAIN) final_T += vo;   // (null without TRAIN)
         if (out_depth) out_depth += vo;
+        if (ALPHA) out_alpha += vo;
         if (ckpt) ckpt += (size_t)ckpt_slots * GGR_CKPT_FLOATS * vo;
     }
 
@@ -241,24 +246,31 @@ blend_fwd_kernel(int W, int H, int grid_x, const uint2* __restrict__ ranges,
         out_color[hw + pid] = C1 + T * bg[1];
         out_color[2 * hw + pid] = C2 + T * bg[2];
         if (out_depth) out_depth[pid] = Dz;
+        if (ALPHA) out_alpha[pid] = 1.0f - T;
     }
 }
 
 void launch_blend_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const float4* splat,
                       const float4* colour,
                       const float* bg, float* out_color, float* final_T, uint32_t* n_contrib,
-                      float* out_depth, float* ckpt, int ckpt_slots, uint32_t* tile_top, int views, int scissored,
-                      void* zero_area, size_t zero_bytes, hipStream_t s) {
+                      float* out_depth, float* out_alpha, float* ckpt, int ckpt_slots, uint32_t* tile_top, int views,
+                      int scissored, void* zero_area, size_t zero_bytes, hipStream_t s) {
     const int gx = (W + GGR_TILE - 1) / GGR_TILE, gy = (H + GGR_TILE - 1) / GGR_TILE;
     if (gx * gy * views == 0) return;
-    // (final_T == nullptr: the caller keeps nothing for a backward)
-#define GGR_LAUNCH_BFWD(TRAIN_)                                                                                              \
-    hipLaunchKernelGGL(blend_fwd_kernel<TRAIN_>, dim3(xcd_grid(gx * gy * views)), dim3(256), 0, s, W, H, gx, ranges, point_list,  \
-                       splat, colour, bg, out_color, final_T, n_contrib, out_depth, ckpt, ckpt_slots, tile_top, views,               \
+    // (final_T == nullptr: the caller keeps nothing for a backward; out_alpha == nullptr: no alpha plane requested)
+#define GGR_LAUNCH_BFWD(TRAIN_, ALPHA_)                                                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(blend_fwd_kernel<TRAIN_, ALPHA_>), dim3(xcd_grid(gx * gy * views)), dim3(256), 0, s, W, H, gx, \
+                       ranges, point_list, splat, colour, bg, out_color, final_T, n_contrib, out_depth, out_alpha, ckpt,         \
+                       ckpt_slots, tile_top, views,                                                                           \
                        xcd_forward_interleaved(gx * gy * views, scissored != 0) ? 1 : 0, (float4*)zero_area,                 \
                        zero_area ? zero_bytes / 16 : 0)
-    if (final_T) GGR_LAUNCH_BFWD(true);
-    else GGR_LAUNCH_BFWD(false);
+    if (out_alpha) {
+        if (final_T) GGR_LAUNCH_BFWD(true, true);
+        else GGR_LAUNCH_BFWD(false, true);
+    } else {
+        if (final_T) GGR_LAUNCH_BFWD(true, false);
+        else GGR_LAUNCH_BFWD(false, false);
+    }
 #undef GGR_LAUNCH_BFWD
 }
 

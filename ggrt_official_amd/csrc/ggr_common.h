@@ -475,7 +475,8 @@ void launch_tile_depth_sort(size_t T, const uint2* ranges, uint32_t* point_list,
 void launch_blend_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const float4* splat,
                       const float4* colour,
                       const float* bg, float* out_color, float* final_T, uint32_t* n_contrib,
-                      float* out_depth, float* ckpt /*or null*/, int ckpt_slots, uint32_t* tile_top, int views,
+                      float* out_depth, float* out_alpha /*or null: 1 − T per pixel, [V,H,W]*/, float* ckpt /*or null*/,
+                      int ckpt_slots, uint32_t* tile_top, int views,
                       int scissored /*the lists are confined to a window of the frame (GgrSettings.scissor)*/,
                       void* zero_area /*or null: also cleared, on the side*/, size_t zero_bytes /*multiple of 16*/,
                       hipStream_t s);
@@ -487,7 +488,9 @@ void blend_bwd_counters(unsigned long long* out4, int reset);
 void launch_blend_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const float4* splat,
                       const float4* colour,
                       const float* bg, const float* final_T, const uint32_t* n_contrib,
-                      const float* dL_dpix, const float* dL_ddepth /*or null*/, float* grad2d /*[P][16], zeroed*/,
+                      const float* dL_dpix, const float* dL_ddepth /*or null*/,
+                      const float* dL_dalpha /*or null: gradient w.r.t. the forward's 1 − T, [V,H,W]*/,
+                      float* grad2d /*[P][16], zeroed*/,
                       const uint32_t* tile_top, const float* ckpt /*or null*/, int ckpt_slots, int segments, int views,
                       hipStream_t s);
 

@@ -82,6 +82,9 @@ class GaussianRasterizationSettings(NamedTuple):
     #                         Gaussian's opacity is scaled by sqrt(det Σ2D / det(Σ2D + 0.3·I)), the growth the 0.3 px² dilation
     #                         gave its footprint (include/ggr_raster.h GgrForwardOptions); differentiated in the backward.
     #                         False: as before.  GGRt's checkpoints were trained without it
+    return_alpha: bool = False  # extension: also return the accumulated opacity alpha = 1 − T per pixel ([H,W]; [V,H,W] from
+    #                         rasterize_views) as a 4th output, differentiable (include/ggr_raster.h GgrForwardExtra) — what
+    #                         gsplat returns as `alphas`.  False: the 3-tuple as before, nothing extra allocated or written
 
 
 class StageProfile:
@@ -130,6 +133,11 @@ def _current_profile():
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
+
+
+def _byref(struct):
+    """ctypes pointer to an optional struct argument (None = NULL)"""
+    return None if struct is None else C.byref(struct)
 
 
 def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -442,6 +450,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             depth = torch.empty((H, W), dtype=torch.float32, device=dev)
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
+            want_alpha = bool(getattr(rs, "return_alpha", False))
+            alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if want_alpha else None
+            extra = _lib.forward_extra(alpha.data_ptr()) if want_alpha else None
             # nothing requires grad (torch.no_grad() / inference): no backward will replay this forward, so the
             # per-pixel checkpoints of the segmented backward are neither written nor allocated
             # (needs_input_grad mirrors tensor.requires_grad even under no_grad — the call site's means2D sink always
@@ -485,8 +496,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             key = (dev.index, P, W, H, 1, _scissor_key(rs)) + _aa_key(aa)
             _sort_choice(key, rs, st)
             _sort_no_buckets(key, st)
-            _forward_with_guess(lambda: lib.ggr_forward_opt(C.byref(st), C.byref(opt), C.byref(fin), C.byref(fout), cb, None,
-                                                            stream),
+            _forward_with_guess(lambda: lib.ggr_forward_ext(C.byref(st), C.byref(opt), _byref(extra), C.byref(fin),
+                                                            C.byref(fout), cb, None, stream),
                                 fout, holder, lib, dev, W, H, key, capacity, prof is not None)
             _sort_look(key, lib, fout, geom, P, stream)
             _sort_fell_back(key, fout)
@@ -506,10 +517,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                               img, holder.get("bin"), aux_c, scratch)
         ctx.scratch_fresh = scratch is not None  # (a second backward over this forward clears a scratch of its own)
         ctx.mark_non_differentiable(radii)
-        return color, radii, depth
+        return (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth):
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch) = ctx.saved_tensors
@@ -522,6 +533,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grad_color = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
             grad_color = _f32c(grad_color)
             grad_depth = _f32c(grad_depth)
+            grad_alpha = _f32c(grad_alpha)   # (None: the default backward kernels)
+            bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
             d_means3D = torch.empty((P, 3), dtype=torch.float32, device=dev)
             d_means2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
             d_op = torch.empty((P,), dtype=torch.float32, device=dev)
@@ -557,7 +570,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             if prof is not None:
                 bout.stage_ms = C.cast(prof.bwd, C.c_void_p)
                 prof.bwd_calls += 1
-            _check(lib.ggr_backward(C.byref(st), C.byref(bin_), C.byref(bout), stream), "ggr_backward")
+            _check(lib.ggr_backward_ext(C.byref(st), _byref(bextra), C.byref(bin_), C.byref(bout), stream), "ggr_backward")
 
         means_shape, sh_shape, op_shape, aux_shape = ctx.in_shapes
         has_sh, has_cp, has_sc, has_cov = ctx.has
@@ -632,6 +645,9 @@ class _RasterizeViews(torch.autograd.Function):
             color = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
             depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
             radii = torch.empty((V, P), dtype=torch.int32, device=dev)
+            want_alpha = bool(getattr(rs, "return_alpha", False))
+            alpha = torch.empty((V, H, W), dtype=torch.float32, device=dev) if want_alpha else None
+            extra = _lib.forward_extra(alpha.data_ptr()) if want_alpha else None
             infer = (not grad_mode) or not any(ctx.needs_input_grad)
             geom = torch.empty((lib.ggr_geom_bytes_inference(P, V) if infer else lib.ggr_geom_bytes_views(P, V),),
                                dtype=torch.uint8, device=dev)
@@ -670,8 +686,8 @@ class _RasterizeViews(torch.autograd.Function):
             key = (dev.index, P, W, H, V, _scissor_key(rs)) + _aa_key(aa)
             _sort_choice(key, rs, st)
             _sort_no_buckets(key, st)
-            _forward_with_guess(lambda: lib.ggr_forward_views_opt(C.byref(st), C.byref(opt), C.byref(vw), C.byref(fin),
-                                                                  C.byref(fout), cb, None, stream),
+            _forward_with_guess(lambda: lib.ggr_forward_views_ext(C.byref(st), C.byref(opt), _byref(extra), C.byref(vw),
+                                                                  C.byref(fin), C.byref(fout), cb, None, stream),
                                 fout, holder, lib, dev, W, H, key, capacity, prof is not None)
             _sort_look(key, lib, fout, geom, P * V, stream)
             _sort_fell_back(key, fout)
@@ -690,10 +706,10 @@ class _RasterizeViews(torch.autograd.Function):
                               img, holder.get("bin"), aux_c, tf_c, sc_in, scratch)
         ctx.scratch_fresh = scratch is not None
         ctx.mark_non_differentiable(radii)
-        return color, radii, depth
+        return (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth):
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, tf, sc_in,
@@ -706,7 +722,8 @@ class _RasterizeViews(torch.autograd.Function):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if grad_color is None:
                 grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
-            grad_color, grad_depth = _f32c(grad_color), _f32c(grad_depth)
+            grad_color, grad_depth, grad_alpha = _f32c(grad_color), _f32c(grad_depth), _f32c(grad_alpha)
+            bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
             form, cov_full, sh_cm = ctx.form
             e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
             d_means3D, d_means2D, d_op = e(PT, 3), e(V, P, 3), e(PT)
@@ -742,8 +759,8 @@ class _RasterizeViews(torch.autograd.Function):
             if prof is not None:
                 bout.stage_ms = C.cast(prof.bwd, C.c_void_p)
                 prof.bwd_calls += 1
-            _check(lib.ggr_backward_views(C.byref(st), C.byref(vw), C.byref(bin_), C.byref(bout), stream),
-                   "ggr_backward_views")
+            _check(lib.ggr_backward_views_ext(C.byref(st), _byref(bextra), C.byref(vw), C.byref(bin_), C.byref(bout),
+                                              stream), "ggr_backward_views")
         means_shape, sh_shape, op_shape, aux_shape, cam_shape, cp_shape, sc_shape, rot_shape, cov_shape = ctx.in_shapes
         has_sh, has_cp, has_sc, has_cov, has_m2d = ctx.has
         return (
@@ -775,7 +792,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     (device tensors: tan(fov/2) per view), ``input_scale [V]`` or None, ``aux_precomp [V,P]`` or None, ``means2D
     [V,P,3]`` or None (only a gradient sink, as at the reference's call site).  ``raster_settings`` supplies the image
     size, ``sh_degree``, ``scale_modifier``, ``debug`` and the extension fields; its per-view fields are ignored.
-    Returns ``(color [V,3,H,W], radii [V,P], depth [V,H,W])``; gradients w.r.t. the Gaussians arrive summed over
+    Returns ``(color [V,3,H,W], radii [V,P], depth [V,H,W])`` — and ``alpha [V,H,W]`` as a 4th output with
+    ``raster_settings.return_alpha``; gradients w.r.t. the Gaussians arrive summed over
     the views, per-view results equal ``GaussianRasterizer``'s (same lists, bit-identical images)."""
     shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
     scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
@@ -863,7 +881,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 class GaussianRasterizer(nn.Module):
     """Drop-in for ``diff_gaussian_rasterization.GaussianRasterizer`` (call site:
     reference ``cuda_splatting.py:114-125``).  Returns the 3-tuple ``(color[3,H,W], radii[P],
-    depth[H,W])`` that the live call site unpacks at ``:118``."""
+    depth[H,W])`` that the live call site unpacks at ``:118`` — with ``return_alpha=True`` in the settings the 4-tuple
+    ``(color, radii, depth, alpha[H,W])``, alpha = 1 − T the accumulated opacity, differentiable."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()

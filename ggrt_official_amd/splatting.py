@@ -83,6 +83,7 @@ class Gaussians:
 class DecoderOutput:
     color: Tensor            # [b, v, 3, h, w]
     depth: Optional[Tensor]  # [b, v, h, w]
+    alpha: Optional[Tensor] = None  # [b, v, h, w]: accumulated opacity 1 − T (DecoderSplattingCUDA(..., return_alpha=True))
 
 
 def get_fov(intrinsics: Tensor) -> Tensor:
@@ -170,7 +171,7 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,
-                       antialiasing=False):
+                       antialiasing=False, return_alpha=False):
     """Everything ``render_cuda`` hands to the rasterizer, batched: a list of
     (GaussianRasterizationSettings, kwargs) per view.  Split out so the golden-vector tests can
     compare it with what the reference's call site produces.
@@ -216,7 +217,7 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
             bg=background_color[i], scale_modifier=1.0, viewmatrix=view[i], projmatrix=full[i],
             sh_degree=degree, campos=extrinsics[i, :3, 3], prefiltered=False,
             sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}),
-            **({"antialiasing": True} if antialiasing else {}))
+            **({"antialiasing": True} if antialiasing else {}), **({"return_alpha": True} if return_alpha else {}))
         kwargs = dict(means3D=gaussian_means[i], shs=shs[i] if use_sh else None,
                       colors_precomp=None if use_sh else shs[i, :, 0, :],
                       opacities=gaussian_opacities[i, ..., None])
@@ -249,7 +250,7 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_means: Tensor, gaussian_covariances: Tensor, gaussian_sh_coefficients: Tensor,
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
-                scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False) -> Tensor:
+                scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False):
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
 
@@ -257,11 +258,18 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     fine-tune loop's deferred back-propagation (``finetune_ggrt_stable.py:126-142``), which renders the whole frame
     per crop cell and slices one cell out.  Inside the window the image equals the full render bit for bit.
 
-    ``antialiasing=True`` (upstream's setting): opacities compensated for the screen-space dilation (``boundary_arguments``)."""
+    ``antialiasing=True`` (upstream's setting): opacities compensated for the screen-space dilation (``boundary_arguments``).
+
+    ``return_alpha=True`` (extension): returns ``(color [batch,3,h,w], alpha [batch,h,w])``, alpha = 1 − T the accumulated
+    opacity of the same pass, differentiable."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
-                               use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing)
-    return torch.stack([o[0] for o in _rasterize_views(calls)])
+                               use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing,
+                               return_alpha)
+    outs = _rasterize_views(calls)
+    if return_alpha:
+        return torch.stack([o[0] for o in outs]), torch.stack([o[3] for o in outs])
+    return torch.stack([o[0] for o in outs])
 
 
 def depth_to_relative_disparity(depth, near, far, eps: float = 1e-10):
@@ -305,7 +313,7 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            depth_mode: DepthRenderingMode = "depth", scale_invariant: bool = True,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
                            gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
-                           antialiasing: bool = False):
+                           antialiasing: bool = False, return_alpha: bool = False):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
 
@@ -313,13 +321,16 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     coefficient, i.e. every Gaussian contributes ``max(0.5 + C0·f(z), 0)`` per channel over a black
     background, and the three identical channels are averaged.  Here that per-Gaussian value is handed to
     the rasterizer as its 4th blended feature (``aux_precomp``), so the depth image is the aux image of the
-    SAME pass: identical values and gradients, half the work.  Returns ([b,3,h,w], [b,h,w])."""
+    SAME pass: identical values and gradients, half the work.  Returns ([b,3,h,w], [b,h,w]) — and the accumulated opacity
+    [b,h,w] of the same pass as a third result with ``return_alpha=True``."""
     feat = depth_feature(extrinsics, gaussian_means, near, far, depth_mode)  # unscaled, as the reference
     aux = (0.5 + SH_C0 * feat).clamp(min=0.0)
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
-                               use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing)
+                               use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing, return_alpha)
     outs = _rasterize_views(calls, aux=aux)
+    if return_alpha:
+        return tuple(torch.stack([o[k] for o in outs]) for k in (0, 2, 3))
     return torch.stack([o[0] for o in outs]), torch.stack([o[2] for o in outs])
 
 
@@ -327,7 +338,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                        background_color: Tensor, gaussians: Gaussians, view_to_batch,
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
-                       sh_max_degree: Optional[int] = None, antialiasing: bool = False):
+                       sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
     * ``device_camera``: view / projection matrices, camera position, tan(fov/2) and 1/near of all views come
@@ -349,7 +360,8 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
 
     Same images and gradients as ``render_color_and_depth`` / ``render_cuda`` up to fp32 rounding
     (``tests/test_callsite_fused.py``).  extrinsics/intrinsics/near/far/background: one row per view.
-    Returns (color [n,3,h,w], depth [n,h,w] | None)."""
+    Returns (color [n,3,h,w], depth [n,h,w] | None) — with ``return_alpha=True`` also alpha [n,h,w], the accumulated
+    opacity 1 − T of the same launches (differentiable)."""
     n = extrinsics.shape[0]
     h, w = image_shape
     d_sh = gaussians.harmonics.shape[-1]
@@ -399,12 +411,14 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             image_height=h, image_width=w, tanfovx=0.0, tanfovy=0.0, bg=background_color[0], scale_modifier=1.0,
             viewmatrix=view[0], projmatrix=full[0], sh_degree=degree, campos=campos[0], prefiltered=False,
             list_capacity=list_capacity * n, sh_channel_major=True, aux_affine=aux_affine,
-            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing))
+            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
+            return_alpha=bool(return_alpha))
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
-        col, _, dep = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
-                                      settings, shs=gaussians.harmonics, aux_precomp=aux, input_scale=scale, **kw)
-        return col, (dep if depth_mode is not None else None)
+        out = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
+                              settings, shs=gaussians.harmonics, aux_precomp=aux, input_scale=scale, **kw)
+        return _fused_result(out[0], out[2] if depth_mode is not None else None, out[3] if return_alpha else None,
+                             return_alpha)
     # batch element b of every Gaussian tensor WITHOUT `t[b]`: select's backward zero-fills a full [B,…] tensor
     # and copies the slice in, per view (0.2 ms per view for 1 M × 25 SH coefficients).  One unbind per tensor
     # (backward = one stack) — or a free reshape when there is a single batch element, GGRt's case.
@@ -415,7 +429,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     g_means, g_cov, g_sh, g_op = (per_batch(gaussians.means), per_batch(gaussians.covariances),
                                   per_batch(gaussians.harmonics), per_batch(gaussians.opacities))
     g_scales, g_rot = per_batch(gaussians.scales), per_batch(gaussians.rotations)
-    colors, depths = [None] * n, [None] * n
+    colors, depths, alphas = [None] * n, [None] * n, [None] * n
     groups = {}
     for i in range(n):
         groups.setdefault(int(view_to_batch[i]), []).append(i)
@@ -441,15 +455,20 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             image_height=h, image_width=w, tanfovx=0.0, tanfovy=0.0, bg=background_color[idx[0]], scale_modifier=1.0,
             viewmatrix=view[idx[0]], projmatrix=full[idx[0]], sh_degree=degree, campos=campos[idx[0]],
             prefiltered=False, list_capacity=list_capacity * len(idx), sh_channel_major=True, aux_affine=aux_affine,
-            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing))
+            sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
+            return_alpha=bool(return_alpha))
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
-        col, _, dep = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
-                                      take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
-                                      input_scale=None if scale is None else take(scale), **kw)
+        out = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
+                              take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
+                              input_scale=None if scale is None else take(scale), **kw)
+        col, dep = out[0], out[2]
         if len(idx) == n and contiguous:  # every view in this one launch set: hand its outputs on as they are
-            return col, (dep if depth_mode is not None else None)
+            return _fused_result(col, dep if depth_mode is not None else None, out[3] if return_alpha else None,
+                                 return_alpha)
         for k, i in enumerate(idx):
             colors[i], depths[i] = col[k], dep[k]
+            if return_alpha:
+                alphas[i] = out[3][k]
     for i in single:
         b = int(view_to_batch[i])
         aux, aux_affine = None, None
@@ -465,7 +484,8 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             campos=campos[i], prefiltered=False, list_capacity=list_capacity,
             input_scale=None if scale is None else scale[i:i + 1], sh_channel_major=True, aux_affine=aux_affine,
             tanfov=None if tanfov is None else tanfov[i], sh_max_degree=sh_cap,
-            scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing))
+            scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
+            return_alpha=bool(return_alpha))
         means = g_means[b]
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
@@ -473,16 +493,25 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         out = GaussianRasterizer(settings)(means3D=means, means2D=sink, opacities=g_op[b][..., None], shs=g_sh[b],
                                            aux_precomp=aux, **kw)
         colors[i], depths[i] = out[0], out[2]
+        if return_alpha:
+            alphas[i] = out[3]
     # one view (GGRt's usual call): a view of the rasterizer's output instead of a stack — no copy kernel forward,
     # none backward
     stack = lambda ts: ts[0].unsqueeze(0) if len(ts) == 1 else torch.stack(ts)
-    return stack(colors), (stack(depths) if depth_mode is not None else None)
+    return _fused_result(stack(colors), stack(depths) if depth_mode is not None else None,
+                         stack(alphas) if return_alpha else None, return_alpha)
+
+
+def _fused_result(color, depth, alpha, return_alpha):
+    """render_views_fused's result: (color, depth) as always, (color, depth, alpha) with return_alpha"""
+    return (color, depth, alpha) if return_alpha else (color, depth)
 
 
 class DecoderSplattingCUDA(nn.Module):
     """Same call contract as reference ``decoder_splatting_cuda.py:19-85``:
     ``forward(gaussians, extrinsics[b,v,4,4], intrinsics[b,v,3,3], near[b,v], far[b,v], image_shape,
-    depth_mode) -> DecoderOutput(color[b,v,3,h,w], depth[b,v,h,w] | None)``."""
+    depth_mode) -> DecoderOutput(color[b,v,3,h,w], depth[b,v,h,w] | None)``; with ``return_alpha=True`` (extension) the
+    output's ``alpha[b,v,h,w]`` holds the accumulated opacity 1 − T of the colour pass, differentiable."""
 
     def __init__(self, cfg=None, fused_depth: bool = True, fused_inputs: bool = True, list_capacity: int = 0,
                  sh_max_degree: Optional[int] = None, antialiasing: bool = False):
@@ -519,37 +548,50 @@ class DecoderSplattingCUDA(nn.Module):
                     gaussian_rotations=cls._per_view(gaussians.rotations, v))
 
     def forward(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
-                image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None) -> DecoderOutput:
+                image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None,
+                return_alpha: bool = False) -> DecoderOutput:
         """``scissor=(x0, y0, x1, y1)`` (extension, fused path): render only that pixel window's tiles — the
-        deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``."""
+        deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``.  ``return_alpha=True`` (extension): the output's
+        ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it."""
         b, v = extrinsics.shape[:2]
+        alpha = None
         if scissor is not None and not (self.fused_inputs and self.fused_depth):
             raise ValueError("scissor needs the fused call site (fused_inputs and fused_depth)")
         bg = self.background_color.to(far.device)[None].expand(b * v, 3)
         if self.fused_inputs and self.fused_depth:
             # no per-view copies of the Gaussians, no torch op on a Gaussian-sized tensor (render_views_fused)
-            color, depth = render_views_fused(
+            out = render_views_fused(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
-                scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing)
+                scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha)
+            color, depth = out[0], out[1]
+            if return_alpha:
+                alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]),
-                                 None if depth is None else depth.reshape(b, v, *depth.shape[1:]))
+                                 None if depth is None else depth.reshape(b, v, *depth.shape[1:]), alpha)
         if depth_mode is not None and self.fused_depth:
-            color, depth = render_color_and_depth(
+            out = render_color_and_depth(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 self._per_view(gaussians.means, v), self._opt_per_view(gaussians.covariances, v),
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
-                sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, **self._ellipsoids(gaussians, v))
-            return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]))
+                sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
+                **self._ellipsoids(gaussians, v))
+            color, depth = out[0], out[1]
+            if return_alpha:
+                alpha = out[2].reshape(b, v, *out[2].shape[1:])
+            return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]), alpha)
         color = render_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                             image_shape, bg, self._per_view(gaussians.means, v),
                             self._opt_per_view(gaussians.covariances, v), self._per_view(gaussians.harmonics, v),
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
-                            antialiasing=self.antialiasing, **self._ellipsoids(gaussians, v))
+                            antialiasing=self.antialiasing, return_alpha=return_alpha, **self._ellipsoids(gaussians, v))
+        if return_alpha:   # (the colour pass's; the reference's separate depth pass below has its own)
+            color, alpha = color
+            alpha = alpha.reshape(b, v, *alpha.shape[1:])
         color = color.reshape(b, v, *color.shape[1:])
         depth = None if depth_mode is None else self.render_depth(gaussians, extrinsics, intrinsics, near, far,
                                                                   image_shape, depth_mode)
-        return DecoderOutput(color, depth)
+        return DecoderOutput(color, depth, alpha)
 
     def render_depth(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                      image_shape, mode: DepthRenderingMode = "depth") -> Tensor:

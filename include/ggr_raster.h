@@ -365,6 +365,51 @@ int ggr_forward_views_opt(const GgrSettings* settings, const GgrForwardOptions* 
 int ggr_backward_views(const GgrSettings* settings, const GgrViews* views, const GgrBackwardIn* in, GgrBackwardOut* out,
                        void* stream);
 
+/* ---- extra output planes: the accumulated opacity (ABI 11, additive: no struct above grows) ---------------------------
+ * alpha[pix] = 1 − T, T the transmittance left behind the pixel's last blended entry — the same T the forward multiplies bg
+ * by (the entry that would push T below 1e-4 is not blended, exactly as for the colour).  So
+ *     out_color = Σ c·α·T + (1 − alpha)·bg   and a pixel without contributors has alpha = 0.
+ * Planes: out_alpha [H,W] for ggr_forward_ext, [V,H,W] for ggr_forward_views_ext (view v at v·H·W, like out_depth);
+ * dL_dout_alpha has the same shape in ggr_backward_ext / ggr_backward_views_ext.  The backward differentiates it exactly:
+ * d alpha / dα_s = T_final / (1 − α_s), the colour's background term with −dL/dalpha in place of bg·dL/dpixel; a pixel whose
+ * only nonzero upstream gradient is dL/dalpha takes part in the backward like any other.  The gradients flow on to every
+ * input as the colour's do (means, covariance / scale / rotation, opacity, camera); colours and SH get none from alpha.
+ * In every mode alpha comes from the blend that wrote the returned colour:
+ *   - exact mode, hinted list buffer, sync-free mode: the forward's one blend; the hint repairs (list buffer or list length
+ *     guessed too small, the bucket form's fault, per-tile → global sort) blend once more and write alpha once more;
+ *   - no_backward (inference): the same values as a training forward, bit for bit;
+ *   - scissor: tiles outside the window have no list entries, so their alpha is 0 (their colour is bg);
+ *   - antialiasing: α is the compensated opacity's, as for the colour;
+ *   - non-finite inputs: a Gaussian excluded by the contract at the top of this file adds nothing to alpha either.
+ * Requesting alpha changes nothing else: not the lists, their sizes or the other outputs (bit for bit), and it needs no
+ * buffer of the library's.  NULL extras = the calls without `_ext`.  A struct_size smaller than the struct, or a nonzero
+ * `reserved`, returns GGR_E_INVALID before anything is enqueued. */
+typedef struct GgrForwardExtra {
+    int32_t struct_size;    /* sizeof(GgrForwardExtra) */
+    int32_t reserved;       /* 0 */
+    float* out_alpha;       /* device [H,W] / [V,H,W] or NULL: no alpha plane (nothing is written) */
+} GgrForwardExtra;
+
+typedef struct GgrBackwardExtra {
+    int32_t struct_size;           /* sizeof(GgrBackwardExtra) */
+    int32_t reserved;              /* 0 */
+    const float* dL_dout_alpha;    /* device [H,W] / [V,H,W] or NULL: no gradient w.r.t. alpha (the default kernels run) */
+} GgrBackwardExtra;
+
+/* ggr_forward_opt / ggr_backward with extra planes (GgrForwardExtra / GgrBackwardExtra; NULL = without them).  The backward
+ * still needs dL_dout_color: pass zeros for an alpha-only loss. */
+int ggr_forward_ext(const GgrSettings* settings, const GgrForwardOptions* options, const GgrForwardExtra* extra,
+                    const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc, void* alloc_ctx, void* stream);
+int ggr_backward_ext(const GgrSettings* settings, const GgrBackwardExtra* extra, const GgrBackwardIn* in,
+                     GgrBackwardOut* out, void* stream);
+
+/* ggr_forward_views_opt / ggr_backward_views with extra planes ([V,H,W]) */
+int ggr_forward_views_ext(const GgrSettings* settings, const GgrForwardOptions* options, const GgrForwardExtra* extra,
+                          const GgrViews* views, const GgrForwardIn* in, GgrForwardOut* out, GgrAllocFn alloc,
+                          void* alloc_ctx, void* stream);
+int ggr_backward_views_ext(const GgrSettings* settings, const GgrBackwardExtra* extra, const GgrViews* views,
+                           const GgrBackwardIn* in, GgrBackwardOut* out, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
