@@ -75,9 +75,12 @@ __device__ __forceinline__ void bucket_sort_one(uint32_t* lds, uint2 range, uint
     if (n > cap) {
         // a bucket of more keys than a workgroup sorts (an overfull fine bin): left in id order — the stable partition's —
         // it is sorted iff all its keys are equal (a plane of constant depth); otherwise the fault bit, and the caller
-        // sorts the frame again in three passes
+        // sorts the frame again in three passes.  "All equal" is a statement about the WHOLE bucket: every thread holds its
+        // keys against the bucket's first one (thread t sees positions ≡ t mod 256 only — keys that repeat with a period
+        // dividing 256, two interleaved planes, look constant to each thread by itself).  No barrier: n is arbitrary here
         if (copy_longer) {
-            uint32_t k_or = 0u, k_and = 0xFFFFFFFFu;
+            const uint32_t k_first = pairs[0].y;   // (uniform)
+            bool differs = false;
             // (one workgroup, n of any size: eight entries per thread and trip, every load of a trip in flight together)
             for (uint32_t i0 = 0; i0 < n; i0 += 8u * 256u) {
                 uint2 e[8], pay[8];
@@ -90,12 +93,12 @@ __device__ __forceinline__ void bucket_sort_one(uint32_t* lds, uint2 range, uint
                     const uint32_t i = i0 + (uint32_t)u * 256u + tid;
                     if (i < n) {
                         list[i] = e[u].x;
-                        k_or |= e[u].y; k_and &= e[u].y;
+                        differs |= e[u].y != k_first;
                         gdst[i] = pay[u];
                     }
                 }
             }
-            if (ex.fault_word && k_or != k_and) atomicOr(ex.fault_word, GGR_FAULT_BUCKET);
+            if (ex.fault_word && differs) atomicOr(ex.fault_word, GGR_FAULT_BUCKET);
         }
         return;
     }

@@ -430,7 +430,9 @@ int ggr_camera_setup(int32_t n, const float* extrinsics /*[n,4,4] camera-to-worl
  *
  * Depth order: the sort key is the float bits of the view depth less those of the near cull (0.2), 30 bits — any
  * depth below 6.8e37 keeps its exact order (ties by ascending index, as the reference's stable 64-bit sort);
- * Gaussians at or beyond 6.8e37 (incl. +inf) share the last key and are ordered by index among themselves.
+ * Gaussians at a finite depth at or beyond 6.8e37 (6.9e37, 1e38, 3e38 … FLT_MAX) share the last key and are ordered by index
+ * among themselves, whatever their depths.  A +inf depth is a non-finite input (the contract at the top of this file wins):
+ * radius 0, in no list.
  * A launch set of up to 64 views sorts one segment per view; beyond 64 views the views share one segment (same
  * lists, slower sort). */
 int ggr_forward_status(const void* geom_buffer, int32_t num_points, int64_t* num_rendered, int32_t* overflow,

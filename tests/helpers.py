@@ -186,3 +186,61 @@ def hip_forward_backward(sc: Scene, dL_dcolor: torch.Tensor, use_sh=True, use_co
     torch.cuda.synchronize()
     grads = {k: (None if v.grad is None else v.grad.detach().cpu().numpy()) for k, v in leaves.items()}
     return color.detach().cpu().numpy(), radii.cpu().numpy(), depth.detach().cpu().numpy(), grads
+
+
+# ---- the depth order of the tile lists, from a forward's own outputs (tests/test_sort_order_reference.py proves these on the
+# C oracle; tests/test_gpu_sort_order.py holds every HIP form of the sort to them) ---------------------------------------------
+SORT_KEY_BASE = 0x3E4CCCCD   # float32 bits of the near cull, 0.2
+SORT_KEY_MAX = 0x3FFFFFFF    # 30 bits: every depth at or beyond 6.8e37 shares this key
+
+
+def sort_key(depth) -> np.ndarray:
+    """The 30-bit depth key of a visible Gaussian (view depth > 0.2): float32 bits less those of 0.2, clamped."""
+    bits = np.ascontiguousarray(np.asarray(depth, np.float32)).view(np.uint32).astype(np.int64)
+    return np.minimum(bits - SORT_KEY_BASE, SORT_KEY_MAX).astype(np.uint32)
+
+
+def order_state(state) -> dict:
+    """depth [P], radii [P], ranges [T, 2], point_list [N], num_rendered as numpy — of an OracleState or of the dict that
+    debug_forward_state returns"""
+    get = (lambda k: state[k]) if isinstance(state, dict) else (lambda k: getattr(state, k))
+    n = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    out = dict(depth=n(get("depth")).astype(np.float32), radii=n(get("radii")), ranges=n(get("ranges")).astype(np.int64),
+               point_list=n(get("point_list")).astype(np.int64))
+    out["num_rendered"] = int(get("num_rendered"))
+    return out
+
+
+def assert_lists_in_depth_order(state):
+    """Every tile's list is in strictly ascending (depth key, Gaussian id) order: the order of a stable sort by (tile, key)
+    over entries emitted in id order.  Strict, because an id occurs once per tile: one comparison covers order and ties."""
+    s = order_state(state)
+    pl, rg = s["point_list"], s["ranges"]
+    assert len(pl) == s["num_rendered"]
+    lens = rg[:, 1] - rg[:, 0]
+    assert (lens >= 0).all() and int(lens.sum()) == len(pl), "the ranges do not tile the list"
+    if len(pl) < 2:
+        return
+    assert pl.min() >= 0 and pl.max() < len(s["depth"])
+    assert (s["radii"][pl] > 0).all(), "a culled Gaussian in a list"
+    k64 = (sort_key(s["depth"])[pl].astype(np.uint64) << np.uint64(32)) | pl.astype(np.uint64)
+    ok = k64[1:] > k64[:-1]
+    starts = rg[lens > 0, 0]
+    ok[starts[starts > 0] - 1] = True          # (the first entry of a range has no predecessor in its tile)
+    if not ok.all():
+        i = int(np.flatnonzero(~ok)[0])
+        tile = int(np.flatnonzero((rg[:, 0] <= i + 1) & (i + 1 < rg[:, 1]))[0])
+        raise AssertionError(f"{int((~ok).sum())} of {len(pl)} list entries are out of (key, id) order; first in tile {tile} at "
+                             f"entry {i + 1}: (key {int(k64[i] >> np.uint64(32)):#x}, id {pl[i]}) before "
+                             f"(key {int(k64[i + 1] >> np.uint64(32)):#x}, id {pl[i + 1]})")
+
+
+def assert_same_members(state_a, state_b):
+    """Same num_rendered, same ranges, and tile by tile the same SET of ids (whatever their order)."""
+    a, b = order_state(state_a), order_state(state_b)
+    assert a["num_rendered"] == b["num_rendered"], (a["num_rendered"], b["num_rendered"])
+    assert np.array_equal(a["ranges"], b["ranges"]), "tile ranges differ"
+    tile = np.repeat(np.arange(len(a["ranges"])), a["ranges"][:, 1] - a["ranges"][:, 0])
+    ma = np.sort((tile << 32) | a["point_list"])
+    mb = np.sort((tile << 32) | b["point_list"])
+    assert np.array_equal(ma, mb), f"{int((ma != mb).sum())} list entries belong to different tiles"
