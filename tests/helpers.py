@@ -122,7 +122,7 @@ def check_grads(grads, ref, keys, tag="", rtol=None, exclude_rows=None):
         assert r <= (GRAD_RTOL if rtol is None else rtol), f"grad {k}: rel-L2 {r:.3e} ({drop} rows set aside; all rows {r_all:.3e})"
 
 
-def oracle_forward(sc: Scene, use_sh=True, use_cov=True, colors=None, sh_cap=3, tight=True):
+def oracle_forward(sc: Scene, use_sh=True, use_cov=True, colors=None, sh_cap=3, tight=True, scale_modifier=1.0):
     """``tight=True``: the oracle with the BUILD's tight tile rects — what the product builds by default, so that lists,
     ranges, num_rendered and n_contrib can be compared entry for entry; ``tight=False``: the reference's rects (the
     restatement proper; the product's ``reference_rects=True``).  Images, final_T, radii and gradients are the same in
@@ -140,7 +140,7 @@ def oracle_forward(sc: Scene, use_sh=True, use_cov=True, colors=None, sh_cap=3, 
         kw["rotations"] = n(sc.rotations)
     return c_oracle.forward(n(sc.means3D), n(sc.opacities), n(sc.viewmatrix), n(sc.projmatrix), n(sc.campos),
                             n(sc.bg), sc.width, sc.height, sc.tanfovx, sc.tanfovy, sh_degree=sc.sh_degree,
-                            sh_cap=sh_cap, tight_rects=tight, **kw)
+                            sh_cap=sh_cap, tight_rects=tight, scale_modifier=scale_modifier, **kw)
 
 
 def rel_l2(a, b) -> float:
@@ -155,8 +155,9 @@ def psnr(a, b) -> float:
 
 
 def hip_forward_backward(sc: Scene, dL_dcolor: torch.Tensor, use_sh=True, use_cov=True, colors=None,
-                         dL_ddepth=None, pose=False, sh_max_degree=3, reference_rects=False):
-    """Runs the product path (GaussianRasterizer on cuda:0).  Returns (color, radii, depth, grads)."""
+                         dL_ddepth=None, pose=False, sh_max_degree=3, reference_rects=False, **settings):
+    """Runs the product path (GaussianRasterizer on cuda:0).  Returns (color, radii, depth, grads).  `settings`: further
+    fields of GaussianRasterizationSettings (scale_modifier, antialiasing, …)."""
     from ggrt_official_amd import GaussianRasterizer
     dev = torch.device("cuda:0")
     s = sc.to(dev)
@@ -173,7 +174,7 @@ def hip_forward_backward(sc: Scene, dL_dcolor: torch.Tensor, use_sh=True, use_co
     else:
         leaves["scales"] = kw["scales"] = leaf(s.scales)
         leaves["rotations"] = kw["rotations"] = leaf(s.rotations)
-    rs = s.settings()._replace(sh_max_degree=sh_max_degree, reference_rects=reference_rects)
+    rs = s.settings()._replace(sh_max_degree=sh_max_degree, reference_rects=reference_rects, **settings)
     if pose:
         view, proj, cam = leaf(s.viewmatrix), leaf(s.projmatrix), leaf(s.campos)
         rs = rs._replace(viewmatrix=view, projmatrix=proj, campos=cam)
