@@ -8,7 +8,8 @@ highest SH band (`ggrt_official_amd.splatting.SH_MAX_DEGREE`: `set_sh_max_degree
 otherwise — INTEGRATION.md §7), silently, exactly as `ggrt_official_amd.splatting.render_cuda` does: the two documented
 integration paths render the same images.  (`ggrt_official_amd.GaussianRasterizer`, the raw rasterizer, keeps "not chosen
 = bands 0..3 with one warning".)  Upstream's `antialiasing=` keyword of the settings passes through unchanged (False by
-default, as upstream), and so does the `return_alpha=` extension (False: the 3-tuple).  Nothing else lives here."""
+default, as upstream), and so do the `return_alpha=` extension (False: the 3-tuple) and the `features_precomp=` keyword of
+the rasterizer call (None: the tuple as it was).  Nothing else lives here."""
 from ggrt_official_amd import rasterizer as _r
 from ggrt_official_amd.rasterizer import GaussianRasterizationSettings  # noqa: F401
 
@@ -28,9 +29,9 @@ class GaussianRasterizer(_r.GaussianRasterizer):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, aux_precomp=None):
+                        raster_settings, aux_precomp=None, features_precomp=None):
     return _r.rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                  _with_call_site_cap(raster_settings), aux_precomp)
+                                  _with_call_site_cap(raster_settings), aux_precomp, features_precomp)
 
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]

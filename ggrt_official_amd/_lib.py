@@ -97,6 +97,22 @@ def backward_extra(dL_dout_alpha=None) -> GgrBackwardExtra:
     return GgrBackwardExtra(struct_size=C.sizeof(GgrBackwardExtra), reserved=0, dL_dout_alpha=dL_dout_alpha)
 
 
+MAX_FEATURES = 32   # GGR_MAX_FEATURES
+
+
+class GgrFeaturePass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("num_features", C.c_int32), ("features", C.c_void_p),
+                ("geom_buffer", C.c_void_p), ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p),
+                ("num_rendered", C.c_int64), ("out_features", C.c_void_p), ("dL_dout_features", C.c_void_p),
+                ("dL_dfeatures", C.c_void_p), ("scratch", C.c_void_p), ("scratch_zeroed", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def feature_pass(**fields) -> GgrFeaturePass:
+    """The argument of ggr_features_forward / ggr_features_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrFeaturePass(struct_size=C.sizeof(GgrFeaturePass), **fields)
+
+
 FWD_STAGES = ["preprocess", "depth_sort", "tile_count", "tile_scatter", "blend", "colour_side_stream", "tile_sort"]
 DEPTH_SORT = {"auto": 0, "global": 1, "per_tile": 2, "global_3pass": 0x101}
 DEPTH_SORT_NO_BUCKETS = 0x100      # IN flag: never the global sort's bucket form (include/ggr_raster.h)
@@ -145,6 +161,8 @@ SYMBOLS = [
                                         C.c_void_p, C.c_void_p]),
     ("ggr_backward_views_ext", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrBackwardExtra), C.POINTER(GgrViews),
                                          C.POINTER(GgrBackwardIn), C.POINTER(GgrBackwardOut), C.c_void_p]),
+    ("ggr_features_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrFeaturePass), C.c_void_p]),
+    ("ggr_features_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrFeaturePass), C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),

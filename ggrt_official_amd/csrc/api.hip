@@ -6,6 +6,7 @@
 // one event for the num_rendered read-back, a side stream — handed back to a process-wide pool when the thread ends (below).
 #include "../../include/ggr_raster.h"
 #include "ggr_common.h"
+#include "blend_feat.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -982,6 +983,81 @@ int ggr_backward_views_ext(const GgrSettings* st, const GgrBackwardExtra* ex, co
 int ggr_backward_views(const GgrSettings* st, const GgrViews* views, const GgrBackwardIn* in, GgrBackwardOut* out,
                        void* stream) {
     return ggr_backward_views_ext(st, nullptr, views, in, out, stream);
+}
+
+// ---- the feature pass (blend_feat.hip): replays of a forward's lists ------------------------------------------------------
+namespace {
+int feature_pass_check(const GgrSettings* st, const GgrViews* views, const GgrFeaturePass* fp, bool backward, int* V, int* vps) {
+    if (!st || !fp) return fail(GGR_E_INVALID, "null settings / feature pass");
+    if (fp->struct_size < (int32_t)sizeof(GgrFeaturePass))
+        return fail(GGR_E_INVALID, "GgrFeaturePass.struct_size %d is smaller than the %d bytes of its fields", (int)fp->struct_size,
+                    (int)sizeof(GgrFeaturePass));
+    if (fp->reserved != 0) return fail(GGR_E_INVALID, "GgrFeaturePass.reserved must be 0, not %d", (int)fp->reserved);
+    if (fp->num_features < 1 || fp->num_features > GGR_MAX_FEATURES)
+        return fail(GGR_E_INVALID, "GgrFeaturePass.num_features must be 1..%d, not %d", GGR_MAX_FEATURES, (int)fp->num_features);
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (!fp->out_features) return fail(GGR_E_INVALID, "GgrFeaturePass.out_features is NULL");
+    if (!fp->geom_buffer || !fp->image_buffer) return fail(GGR_E_INVALID, "GgrFeaturePass: null geom / image buffer of the forward");
+    if (st->num_points > 0 && !fp->features) return fail(GGR_E_INVALID, "GgrFeaturePass.features is NULL");
+    if (fp->num_rendered != 0 && !fp->binning_buffer) return fail(GGR_E_INVALID, "GgrFeaturePass.binning_buffer is NULL");
+    if (backward) {
+        if (!fp->dL_dout_features) return fail(GGR_E_INVALID, "GgrFeaturePass.dL_dout_features is NULL");
+        if (st->num_points > 0 && !fp->dL_dfeatures) return fail(GGR_E_INVALID, "GgrFeaturePass.dL_dfeatures is NULL");
+        if (!fp->scratch) return fail(GGR_E_INVALID, "GgrFeaturePass.scratch is NULL");
+    }
+    *V = 1; *vps = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        *V = views->num_views; *vps = views->num_views / sets;
+    }
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_features_forward(const GgrSettings* st, const GgrViews* views, const GgrFeaturePass* fp, void* stream) {
+    g_err[0] = 0;
+    int V = 1, vps = 1;
+    const int rc = feature_pass_check(st, views, fp, false, &V, &vps);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height, K = fp->num_features;
+    if ((size_t)W * H == 0) return GGR_OK;
+    if (P1 == 0 || fp->num_rendered == 0) {   // no list entry anywhere: every plane is zero
+        HIP_TRY(hipMemsetAsync(fp->out_features, 0, (size_t)V * K * W * H * sizeof(float), s));
+        return GGR_OK;
+    }
+    GeomLayout g = ggr_carve_geom((void*)fp->geom_buffer, (size_t)P1 * V, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)fp->image_buffer, W, H, V);
+    const bool scissored = (st->scissor[0] | st->scissor[1] | st->scissor[2] | st->scissor[3]) != 0;
+    ggr::launch_blend_feat_fwd(W, H, im.ranges, (const uint32_t*)fp->binning_buffer, g.splat, fp->features, K, P1, vps,
+                               fp->out_features, V, scissored ? 1 : 0, s);
+    KCHECK(st->debug != 0, s, "blend_feat_fwd");
+    return GGR_OK;
+}
+
+int ggr_features_backward(const GgrSettings* st, const GgrViews* views, const GgrFeaturePass* fp, void* stream) {
+    g_err[0] = 0;
+    int V = 1, vps = 1;
+    const int rc = feature_pass_check(st, views, fp, true, &V, &vps);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height, K = fp->num_features;
+    BwdScratch sc = ggr_carve_bwd(fp->scratch, (size_t)P1, (size_t)V);
+    if (!fp->scratch_zeroed) HIP_TRY(hipMemsetAsync(fp->scratch, 0, sc.bytes, s));
+    if (P1 == 0) return GGR_OK;
+    HIP_TRY(hipMemsetAsync(fp->dL_dfeatures, 0, (size_t)(V / vps) * P1 * K * sizeof(float), s));
+    if (fp->num_rendered == 0 || (size_t)W * H == 0) return GGR_OK;
+    GeomLayout g = ggr_carve_geom((void*)fp->geom_buffer, (size_t)P1 * V, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)fp->image_buffer, W, H, V);
+    ggr::launch_blend_feat_bwd(W, H, im.ranges, (const uint32_t*)fp->binning_buffer, g.splat, fp->features, K, P1, vps,
+                               fp->out_features, fp->dL_dout_features, fp->dL_dfeatures, sc.grad2d, V, s);
+    KCHECK(st->debug != 0, s, "blend_feat_bwd");
+    return GGR_OK;
 }
 
 size_t ggr_geom_bytes_inference(int32_t P, int32_t V) {

@@ -161,6 +161,33 @@ def _check(rc: int, what: str):
         raise RuntimeError(f"{what} failed (code {rc}): {_lib.last_error()}")
 
 
+def _features_2d(features, rows: int, what: str):
+    """`features_precomp` as a contiguous float32 [rows, K] tensor (1 <= K <= 32); raises on any other shape."""
+    f = _f32c(features)
+    if f.dim() != 2 or f.shape[0] != rows or not (1 <= f.shape[1] <= _lib.MAX_FEATURES):
+        raise RuntimeError(f"{what}: features_precomp must be [{rows}, K] with 1 <= K <= {_lib.MAX_FEATURES}, "
+                           f"not {tuple(features.shape)}")
+    return f
+
+
+def _features_forward(lib, st, vw, feat, geom, img, binb, num_rendered, out, stream):
+    """ggr_features_forward over the buffers of the forward that has just returned (include/ggr_raster.h)."""
+    fp = _lib.feature_pass(num_features=int(feat.shape[1]), features=feat.data_ptr(), geom_buffer=geom.data_ptr(),
+                           image_buffer=img.data_ptr(), binning_buffer=_ptr(binb), num_rendered=int(num_rendered),
+                           out_features=out.data_ptr())
+    _check(lib.ggr_features_forward(C.byref(st), _byref(vw), C.byref(fp), stream), "ggr_features_forward")
+
+
+def _features_backward(lib, st, vw, feat, geom, img, binb, num_rendered, out, grad_out, d_feat, scratch, zeroed, stream):
+    """ggr_features_backward: the feature loss's terms go into `scratch` ahead of ggr_backward*, which is then told that the
+    scratch is in use (scratch_zeroed = 1)."""
+    fp = _lib.feature_pass(num_features=int(feat.shape[1]), features=feat.data_ptr(), geom_buffer=geom.data_ptr(),
+                           image_buffer=img.data_ptr(), binning_buffer=_ptr(binb), num_rendered=int(num_rendered),
+                           out_features=out.data_ptr(), dL_dout_features=grad_out.data_ptr(), dL_dfeatures=d_feat.data_ptr(),
+                           scratch=scratch.data_ptr(), scratch_zeroed=int(zeroed))
+    _check(lib.ggr_features_backward(C.byref(st), _byref(vw), C.byref(fp), stream), "ggr_features_backward")
+
+
 # ---- the default mode's list buffer, sized from what the same shape needed before --------------------------------
 # Upstream's forward reads num_rendered back in the middle, allocates the list buffer to that size and only then
 # launches the rest — the device idles for as long as the host takes (a slow or busy host: 0.96 instead of 0.88 ms per
@@ -416,7 +443,7 @@ def _settings_struct(rs: GaussianRasterizationSettings, P: int, M: int, bg, view
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                viewmatrix, projmatrix, campos, aux, raster_settings, grad_mode=True):
+                viewmatrix, projmatrix, campos, aux, raster_settings, grad_mode=True, features=None):
         lib = _lib.load()
         rs = raster_settings
         dev = means3D.device
@@ -430,6 +457,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         op_c = _f32c(opacities)
         sc_c, rot_c, cov_c = _f32c(scales), _f32c(rotations), _f32c(cov3Ds_precomp)
         aux_c = _f32c(aux)
+        feat_c = None if features is None else _features_2d(features, P, "GaussianRasterizer")
         sh_cm = bool(getattr(rs, "sh_channel_major", False)) and sh_c is not None
         if sh_cm and (sh_c.dim() != 3 or sh_c.shape[1] != 3):
             raise RuntimeError("sh_channel_major expects shs of shape [P,3,M]")
@@ -501,6 +529,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                                 fout, holder, lib, dev, W, H, key, capacity, prof is not None)
             _sort_look(key, lib, fout, geom, P, stream)
             _sort_fell_back(key, fout)
+            feat_out = None
+            if feat_c is not None:   # K feature channels over the lists this forward has just built (csrc/blend_feat.hip)
+                feat_out = torch.empty((feat_c.shape[1], H, W), dtype=torch.float32, device=dev)
+                _features_forward(lib, st, None, feat_c, geom, img, holder.get("bin"), fout.num_rendered, feat_out, stream)
 
         # exact mode: count known, nothing to keep.  Sync-free mode: count + flags live in the geometry buffer on the
         # device, so that (≈100 MB at P = 1 M) buffer stays referenced until this thread's next forward
@@ -514,16 +546,22 @@ class _RasterizeGaussians(torch.autograd.Function):
                          None if aux is None else aux.shape)
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg, view, proj, cam, radii, geom,
-                              img, holder.get("bin"), aux_c, scratch)
+                              img, holder.get("bin"), aux_c, scratch, feat_c, feat_out)
         ctx.scratch_fresh = scratch is not None  # (a second backward over this forward clears a scratch of its own)
         ctx.mark_non_differentiable(radii)
-        return (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
+        ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape)
+        out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
+        return out + (feat_out,) if feat_c is not None else out
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
+    def backward(ctx, grad_color, _grad_radii, grad_depth, *grad_extra):
         lib = _lib.load()
         rs = ctx.raster_settings
-        (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch) = ctx.saved_tensors
+        (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch, feat,
+         feat_out) = ctx.saved_tensors
+        want_alpha, has_feat, feat_shape = ctx.outs
+        grad_alpha = grad_extra[0] if want_alpha else None
+        grad_feat = grad_extra[-1] if has_feat else None
         P, M, H, W = ctx.dims
         dev = means3D.device
         need_pose = any(ctx.needs_input_grad[8:11])
@@ -554,6 +592,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             scratch = fwd_scratch if zeroed else torch.empty((lib.ggr_backward_scratch_bytes(P),), dtype=torch.uint8, device=dev)
 
             st = _settings_struct(rs, P, M, bg, view, proj, cam)
+            d_feat = None
+            if grad_feat is not None:   # the feature loss's terms first: they meet the colour's in the scratch records
+                d_feat = torch.empty_like(feat)
+                _features_backward(lib, st, None, feat, geom, img, binb, ctx.num_rendered, feat_out, _f32c(grad_feat), d_feat,
+                                   scratch, zeroed, stream)
+                zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
                                       scales=_ptr(sc), rotations=_ptr(rot), cov3D_precomp=_ptr(cov),
@@ -588,6 +632,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_cam.reshape(ctx.saved_tensors[10].shape) if ctx.needs_input_grad[10] else None,
             d_aux.reshape(aux_shape) if d_aux is not None else None,
             None, None,
+            d_feat.reshape(feat_shape) if d_feat is not None else None,
         )
 
 
@@ -596,7 +641,7 @@ class _RasterizeViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
-                projmatrices, campos, aux, means2D, raster_settings, bg, tanfov, input_scale, grad_mode=True):
+                projmatrices, campos, aux, means2D, raster_settings, bg, tanfov, input_scale, grad_mode=True, features=None):
         lib = _lib.load()
         rs = raster_settings
         dev = means3D.device
@@ -628,6 +673,11 @@ class _RasterizeViews(torch.autograd.Function):
             means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c = (flat(t) for t in (means3D_c, sh_c, cp_c, op_c, sc_c,
                                                                                    rot_c, cov_c))
         P = means3D_c.shape[0] // B   # Gaussians per set
+        feat_c = None
+        if features is not None:   # [P,K], or [B,P,K] with Gaussian sets: one feature set shared by a set's views
+            if (features.dim() == 3) != (means3D.dim() == 3) or (features.dim() == 3 and features.shape[0] != B):
+                raise RuntimeError("rasterize_views: features_precomp must be [P,K], or [B,P,K] with means3D [B,P,3]")
+            feat_c = _features_2d(features.reshape(-1, features.shape[-1]), B * P, "rasterize_views")
         if aux_c is not None and aux_c.numel() != V * P:
             raise RuntimeError("rasterize_views: aux_precomp must be [V,P]")
         sh_cm = bool(getattr(rs, "sh_channel_major", False)) and sh_c is not None
@@ -691,6 +741,10 @@ class _RasterizeViews(torch.autograd.Function):
                                 fout, holder, lib, dev, W, H, key, capacity, prof is not None)
             _sort_look(key, lib, fout, geom, P * V, stream)
             _sort_fell_back(key, fout)
+            feat_out = None
+            if feat_c is not None:
+                feat_out = torch.empty((V, feat_c.shape[1], H, W), dtype=torch.float32, device=dev)
+                _features_forward(lib, st, vw, feat_c, geom, img, holder.get("bin"), fout.num_rendered, feat_out, stream)
         _tls.last_forward = (geom, P * V) if capacity > 0 else (None, int(fout.num_rendered))
         _tls.last_binning = (int(fout.depth_sort_used), int(fout.max_list_len))
         ctx.raster_settings = rs
@@ -703,17 +757,22 @@ class _RasterizeViews(torch.autograd.Function):
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None,
                    means2D is not None)
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg_c, view, proj, cam, radii, geom,
-                              img, holder.get("bin"), aux_c, tf_c, sc_in, scratch)
+                              img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out)
         ctx.scratch_fresh = scratch is not None
         ctx.mark_non_differentiable(radii)
-        return (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
+        ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape)
+        out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
+        return out + (feat_out,) if feat_c is not None else out
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
+    def backward(ctx, grad_color, _grad_radii, grad_depth, *grad_extra):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, tf, sc_in,
-         fwd_scratch) = ctx.saved_tensors
+         fwd_scratch, feat, feat_out) = ctx.saved_tensors
+        want_alpha, has_feat, feat_shape = ctx.outs
+        grad_alpha = grad_extra[0] if want_alpha else None
+        grad_feat = grad_extra[-1] if has_feat else None
         P, M, H, W, V, B = ctx.dims
         PT = P * B   # rows of the flat [B·P, …] gradient arrays
         dev = means3D.device
@@ -743,6 +802,12 @@ class _RasterizeViews(torch.autograd.Function):
             st = _settings_struct(rs._replace(tanfovx=0.0, tanfovy=0.0, tanfov=None), P, M, None, None, None, None)
             vw = _lib.GgrViews(num_views=V, viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=cam.data_ptr(),
                                bg=bg.data_ptr(), tanfov=tf.data_ptr(), input_scale=_ptr(sc_in), num_sets=B)
+            d_feat = None
+            if grad_feat is not None:
+                d_feat = torch.empty_like(feat)
+                _features_backward(lib, st, vw, feat, geom, img, binb, ctx.num_rendered, feat_out, _f32c(grad_feat), d_feat,
+                                   scratch, zeroed, stream)
+                zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
                                       scales=_ptr(sc), rotations=_ptr(rot), cov3D_precomp=_ptr(cov),
@@ -777,12 +842,13 @@ class _RasterizeViews(torch.autograd.Function):
             d_aux.reshape(aux_shape) if d_aux is not None else None,
             d_means2D if has_m2d else None,
             None, None, None, None, None,
+            d_feat.reshape(feat_shape) if d_feat is not None else None,
         )
 
 
 def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, tanfov, raster_settings, shs=None,
                     colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, aux_precomp=None,
-                    input_scale=None, means2D=None):
+                    input_scale=None, means2D=None, features_precomp=None):
     """V views in ONE launch set — of the SAME Gaussians (``means3D [P,3]``), or, with ``means3D
     [B,P,3]`` and every per-Gaussian input ``[B,P,…]``, of B Gaussian sets with V/B consecutive views each (the
     reference's ``(b v)`` flattening with per-batch-element Gaussians, ``decoder_splatting_cuda.py:40-60``; gradients
@@ -794,7 +860,10 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     size, ``sh_degree``, ``scale_modifier``, ``debug`` and the extension fields; its per-view fields are ignored.
     Returns ``(color [V,3,H,W], radii [V,P], depth [V,H,W])`` — and ``alpha [V,H,W]`` as a 4th output with
     ``raster_settings.return_alpha``; gradients w.r.t. the Gaussians arrive summed over
-    the views, per-view results equal ``GaussianRasterizer``'s (same lists, bit-identical images)."""
+    the views, per-view results equal ``GaussianRasterizer``'s (same lists, bit-identical images).
+    ``features_precomp [P,K]`` (``[B,P,K]`` with Gaussian sets; 1 <= K <= 32): K more per-Gaussian channels composited in
+    one pass over the same lists — ``features [V,K,H,W]`` (Σ f·α·T, no background) is then appended as the LAST output,
+    differentiable like the colour."""
     shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
     scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
     if (shs is None) == (colors_precomp is None):
@@ -804,7 +873,7 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
         raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
     return _RasterizeViews.apply(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                  viewmatrices, projmatrices, campos, aux_precomp, means2D, raster_settings, bg, tanfov,
-                                 input_scale, torch.is_grad_enabled())
+                                 input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))
 
 
 def camera_setup(extrinsics: torch.Tensor, intrinsics: torch.Tensor, near: torch.Tensor, far: torch.Tensor,
@@ -870,12 +939,12 @@ def last_forward_binning():
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, aux_precomp=None):
-    """Function form, argument order of upstream's ``rasterize_gaussians`` (+ the optional aux feature)."""
+                        raster_settings, aux_precomp=None, features_precomp=None):
+    """Function form, argument order of upstream's ``rasterize_gaussians`` (+ the optional aux feature and feature channels)."""
     rs = raster_settings
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
-                                     torch.is_grad_enabled())
+                                     torch.is_grad_enabled(), _none_if_empty(features_precomp))
 
 
 class GaussianRasterizer(nn.Module):
@@ -904,10 +973,12 @@ class GaussianRasterizer(nn.Module):
         return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, aux_precomp=None):
+                cov3D_precomp=None, aux_precomp=None, features_precomp=None):
         """``aux_precomp`` [P] (extension, optional): a 4th feature blended like a colour channel; the third
         return value then is Σ aux·α·T instead of Σ z·α·T (one rasterization serves GGRt's colour AND depth
-        pass — see ``splatting.render_color_and_depth``)."""
+        pass — see ``splatting.render_color_and_depth``).  ``features_precomp`` [P,K] (extension, optional, 1 <= K <= 32):
+        K more per-Gaussian channels rendered in ONE pass over the lists of this call — the returned tuple then grows by
+        ``features [K,H,W]`` = Σ f·α·T (no background term) as its LAST element, differentiable."""
         shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
         scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
@@ -916,7 +987,7 @@ class GaussianRasterizer(nn.Module):
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, self._settings_for_call(), aux_precomp)
+                                   cov3D_precomp, self._settings_for_call(), aux_precomp, features_precomp)
 
     def _settings_for_call(self) -> GaussianRasterizationSettings:
         """The settings a forward runs with (the `diff_gaussian_rasterization` import shim fills in its SH-cap default here)."""

@@ -84,6 +84,7 @@ class DecoderOutput:
     color: Tensor            # [b, v, 3, h, w]
     depth: Optional[Tensor]  # [b, v, h, w]
     alpha: Optional[Tensor] = None  # [b, v, h, w]: accumulated opacity 1 − T (DecoderSplattingCUDA(..., return_alpha=True))
+    features: Optional[Tensor] = None  # [b, v, K, h, w]: Σ f·α·T of the per-Gaussian channels (…, gaussian_features=[b,g,K])
 
 
 def get_fov(intrinsics: Tensor) -> Tensor:
@@ -229,7 +230,7 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
     return out
 
 
-def _rasterize_views(calls, aux=None):
+def _rasterize_views(calls, aux=None, features=None):
     """Runs the per-view rasterizer calls of a batch, serially like the reference's loop
     (``cuda_splatting.py:93-127``) but without its two ``.item()`` syncs per view.
 
@@ -242,6 +243,8 @@ def _rasterize_views(calls, aux=None):
     for i, (settings, kw) in enumerate(calls):
         mean_gradients = torch.zeros_like(kw["means3D"], requires_grad=True)  # the `means2D` gradient sink
         extra = {} if aux is None else {"aux_precomp": aux[i]}
+        if features is not None:   # K more channels over the same lists: the call's tuple grows by features [K,h,w], last
+            extra["features_precomp"] = features[i]
         outs.append(GaussianRasterizer(settings)(means2D=mean_gradients, **kw, **extra))
     return outs
 
@@ -250,7 +253,8 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_means: Tensor, gaussian_covariances: Tensor, gaussian_sh_coefficients: Tensor,
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
-                scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False):
+                scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
+                gaussian_features: Optional[Tensor] = None):
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
 
@@ -261,15 +265,21 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     ``antialiasing=True`` (upstream's setting): opacities compensated for the screen-space dilation (``boundary_arguments``).
 
     ``return_alpha=True`` (extension): returns ``(color [batch,3,h,w], alpha [batch,h,w])``, alpha = 1 − T the accumulated
-    opacity of the same pass, differentiable."""
+    opacity of the same pass, differentiable.
+
+    ``gaussian_features [batch,g,K]`` (extension, 1 <= K <= 32): K per-Gaussian channels composited in one pass over the same
+    lists; the result becomes a tuple whose LAST element is ``features [batch,K,h,w]`` (Σ f·α·T, no background)."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing,
                                return_alpha)
-    outs = _rasterize_views(calls)
+    outs = _rasterize_views(calls, features=gaussian_features)
+    res = (torch.stack([o[0] for o in outs]),)
     if return_alpha:
-        return torch.stack([o[0] for o in outs]), torch.stack([o[3] for o in outs])
-    return torch.stack([o[0] for o in outs])
+        res += (torch.stack([o[3] for o in outs]),)
+    if gaussian_features is not None:
+        res += (torch.stack([o[-1] for o in outs]),)
+    return res if len(res) > 1 else res[0]
 
 
 def depth_to_relative_disparity(depth, near, far, eps: float = 1e-10):
@@ -313,7 +323,8 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            depth_mode: DepthRenderingMode = "depth", scale_invariant: bool = True,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
                            gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
-                           antialiasing: bool = False, return_alpha: bool = False):
+                           antialiasing: bool = False, return_alpha: bool = False,
+                           gaussian_features: Optional[Tensor] = None):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
 
@@ -322,23 +333,26 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     background, and the three identical channels are averaged.  Here that per-Gaussian value is handed to
     the rasterizer as its 4th blended feature (``aux_precomp``), so the depth image is the aux image of the
     SAME pass: identical values and gradients, half the work.  Returns ([b,3,h,w], [b,h,w]) — and the accumulated opacity
-    [b,h,w] of the same pass as a third result with ``return_alpha=True``."""
+    [b,h,w] of the same pass as a third result with ``return_alpha=True``; with ``gaussian_features [b,g,K]`` the rendered
+    ``features [b,K,h,w]`` of the same pass as the LAST result."""
     feat = depth_feature(extrinsics, gaussian_means, near, far, depth_mode)  # unscaled, as the reference
     aux = (0.5 + SH_C0 * feat).clamp(min=0.0)
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing, return_alpha)
-    outs = _rasterize_views(calls, aux=aux)
-    if return_alpha:
-        return tuple(torch.stack([o[k] for o in outs]) for k in (0, 2, 3))
-    return torch.stack([o[0] for o in outs]), torch.stack([o[2] for o in outs])
+    outs = _rasterize_views(calls, aux=aux, features=gaussian_features)
+    picks = (0, 2, 3) if return_alpha else (0, 2)
+    if gaussian_features is not None:
+        picks += (-1,)
+    return tuple(torch.stack([o[k] for o in outs]) for k in picks)
 
 
 def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape,
                        background_color: Tensor, gaussians: Gaussians, view_to_batch,
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
-                       sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False):
+                       sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
+                       gaussian_features: Optional[Tensor] = None):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
     * ``device_camera``: view / projection matrices, camera position, tan(fov/2) and 1/near of all views come
@@ -361,8 +375,10 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     Same images and gradients as ``render_color_and_depth`` / ``render_cuda`` up to fp32 rounding
     (``tests/test_callsite_fused.py``).  extrinsics/intrinsics/near/far/background: one row per view.
     Returns (color [n,3,h,w], depth [n,h,w] | None) — with ``return_alpha=True`` also alpha [n,h,w], the accumulated
-    opacity 1 − T of the same launches (differentiable)."""
+    opacity 1 − T of the same launches (differentiable); with ``gaussian_features [b,g,K]`` (one feature set per batch
+    element, shared by its views) also ``features [n,K,h,w]``, rendered through the same launch sets, as the LAST result."""
     n = extrinsics.shape[0]
+    has_feat = gaussian_features is not None
     h, w = image_shape
     d_sh = gaussians.harmonics.shape[-1]
     degree = isqrt(d_sh) - 1
@@ -416,9 +432,10 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
         out = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
-                              settings, shs=gaussians.harmonics, aux_precomp=aux, input_scale=scale, **kw)
+                              settings, shs=gaussians.harmonics, aux_precomp=aux, input_scale=scale,
+                              features_precomp=gaussian_features, **kw)
         return _fused_result(out[0], out[2] if depth_mode is not None else None, out[3] if return_alpha else None,
-                             return_alpha)
+                             return_alpha, out[-1] if has_feat else None)
     # batch element b of every Gaussian tensor WITHOUT `t[b]`: select's backward zero-fills a full [B,…] tensor
     # and copies the slice in, per view (0.2 ms per view for 1 M × 25 SH coefficients).  One unbind per tensor
     # (backward = one stack) — or a free reshape when there is a single batch element, GGRt's case.
@@ -428,8 +445,8 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         return [t.reshape(t.shape[1:])] if t.shape[0] == 1 else list(t.unbind(0))
     g_means, g_cov, g_sh, g_op = (per_batch(gaussians.means), per_batch(gaussians.covariances),
                                   per_batch(gaussians.harmonics), per_batch(gaussians.opacities))
-    g_scales, g_rot = per_batch(gaussians.scales), per_batch(gaussians.rotations)
-    colors, depths, alphas = [None] * n, [None] * n, [None] * n
+    g_scales, g_rot, g_feat = per_batch(gaussians.scales), per_batch(gaussians.rotations), per_batch(gaussian_features)
+    colors, depths, alphas, feats = [None] * n, [None] * n, [None] * n, [None] * n
     groups = {}
     for i in range(n):
         groups.setdefault(int(view_to_batch[i]), []).append(i)
@@ -460,13 +477,16 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         out = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
                               take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
-                              input_scale=None if scale is None else take(scale), **kw)
+                              input_scale=None if scale is None else take(scale),
+                              features_precomp=g_feat[b] if has_feat else None, **kw)
         col, dep = out[0], out[2]
         if len(idx) == n and contiguous:  # every view in this one launch set: hand its outputs on as they are
             return _fused_result(col, dep if depth_mode is not None else None, out[3] if return_alpha else None,
-                                 return_alpha)
+                                 return_alpha, out[-1] if has_feat else None)
         for k, i in enumerate(idx):
             colors[i], depths[i] = col[k], dep[k]
+            if has_feat:
+                feats[i] = out[-1][k]
             if return_alpha:
                 alphas[i] = out[3][k]
     for i in single:
@@ -491,20 +511,24 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
         sink = torch.empty_like(means).requires_grad_()
         out = GaussianRasterizer(settings)(means3D=means, means2D=sink, opacities=g_op[b][..., None], shs=g_sh[b],
-                                           aux_precomp=aux, **kw)
+                                           aux_precomp=aux, features_precomp=g_feat[b] if has_feat else None, **kw)
         colors[i], depths[i] = out[0], out[2]
+        if has_feat:
+            feats[i] = out[-1]
         if return_alpha:
             alphas[i] = out[3]
     # one view (GGRt's usual call): a view of the rasterizer's output instead of a stack — no copy kernel forward,
     # none backward
     stack = lambda ts: ts[0].unsqueeze(0) if len(ts) == 1 else torch.stack(ts)
     return _fused_result(stack(colors), stack(depths) if depth_mode is not None else None,
-                         stack(alphas) if return_alpha else None, return_alpha)
+                         stack(alphas) if return_alpha else None, return_alpha, stack(feats) if has_feat else None)
 
 
-def _fused_result(color, depth, alpha, return_alpha):
-    """render_views_fused's result: (color, depth) as always, (color, depth, alpha) with return_alpha"""
-    return (color, depth, alpha) if return_alpha else (color, depth)
+def _fused_result(color, depth, alpha, return_alpha, features=None):
+    """render_views_fused's result: (color, depth) as always, (color, depth, alpha) with return_alpha; the rendered feature
+    channels, when asked for, come last"""
+    res = (color, depth, alpha) if return_alpha else (color, depth)
+    return res if features is None else res + (features,)
 
 
 class DecoderSplattingCUDA(nn.Module):
@@ -549,12 +573,16 @@ class DecoderSplattingCUDA(nn.Module):
 
     def forward(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                 image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None,
-                return_alpha: bool = False) -> DecoderOutput:
+                return_alpha: bool = False, gaussian_features: Optional[Tensor] = None) -> DecoderOutput:
         """``scissor=(x0, y0, x1, y1)`` (extension, fused path): render only that pixel window's tiles — the
         deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``.  ``return_alpha=True`` (extension): the output's
-        ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it."""
+        ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it.
+        ``gaussian_features`` [b,g,K] (extension, 1 <= K <= 32): the output's ``features`` [b,v,K,h,w] holds those per-Gaussian
+        channels composited through the colour pass's own launch set (Σ f·α·T, no background), differentiable."""
         b, v = extrinsics.shape[:2]
         alpha = None
+        has_feat = gaussian_features is not None
+        unflat = lambda t: t.reshape(b, v, *t.shape[1:])
         if scissor is not None and not (self.fused_inputs and self.fused_depth):
             raise ValueError("scissor needs the fused call site (fused_inputs and fused_depth)")
         bg = self.background_color.to(far.device)[None].expand(b * v, 3)
@@ -563,35 +591,42 @@ class DecoderSplattingCUDA(nn.Module):
             out = render_views_fused(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
-                scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha)
+                scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
+                gaussian_features=gaussian_features)
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]),
-                                 None if depth is None else depth.reshape(b, v, *depth.shape[1:]), alpha)
+                                 None if depth is None else depth.reshape(b, v, *depth.shape[1:]), alpha,
+                                 unflat(out[-1]) if has_feat else None)
         if depth_mode is not None and self.fused_depth:
             out = render_color_and_depth(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 self._per_view(gaussians.means, v), self._opt_per_view(gaussians.covariances, v),
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
                 sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
-                **self._ellipsoids(gaussians, v))
+                gaussian_features=self._opt_per_view(gaussian_features, v), **self._ellipsoids(gaussians, v))
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
-            return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]), alpha)
+            return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]), alpha,
+                                 unflat(out[-1]) if has_feat else None)
         color = render_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                             image_shape, bg, self._per_view(gaussians.means, v),
                             self._opt_per_view(gaussians.covariances, v), self._per_view(gaussians.harmonics, v),
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
-                            antialiasing=self.antialiasing, return_alpha=return_alpha, **self._ellipsoids(gaussians, v))
+                            antialiasing=self.antialiasing, return_alpha=return_alpha,
+                            gaussian_features=self._opt_per_view(gaussian_features, v), **self._ellipsoids(gaussians, v))
+        features = None
+        if has_feat:
+            color, features = color[:-1] if return_alpha else color[0], unflat(color[-1])
         if return_alpha:   # (the colour pass's; the reference's separate depth pass below has its own)
             color, alpha = color
             alpha = alpha.reshape(b, v, *alpha.shape[1:])
         color = color.reshape(b, v, *color.shape[1:])
         depth = None if depth_mode is None else self.render_depth(gaussians, extrinsics, intrinsics, near, far,
                                                                   image_shape, depth_mode)
-        return DecoderOutput(color, depth, alpha)
+        return DecoderOutput(color, depth, alpha, features)
 
     def render_depth(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                      image_shape, mode: DepthRenderingMode = "depth") -> Tensor:

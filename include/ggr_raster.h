@@ -410,6 +410,46 @@ int ggr_forward_views_ext(const GgrSettings* settings, const GgrForwardOptions* 
 int ggr_backward_views_ext(const GgrSettings* settings, const GgrBackwardExtra* extra, const GgrViews* views,
                            const GgrBackwardIn* in, GgrBackwardOut* out, void* stream);
 
+/* ---- the feature pass: K per-Gaussian channels composited over a forward's lists (ABI 11, additive) -----------------------
+ * out_features[k][pix] = Σ f_k·α·T over the pixel's blended entries — the colour blend's sum with the Gaussian's k-th feature
+ * in place of a colour channel, the same α, T, skip and stop rules, the same weights bit for bit, and NO background term
+ * (like out_depth; a host composes one with alpha).  What the reference's rasterizer needs ⌈K/3⌉ whole calls for — each with
+ * its own preprocess, sort, list build, blend and backward — is here ONE replay of the lists the forward already built.
+ *
+ * Protocol.  ggr_features_forward runs AFTER ggr_forward* (any variant) on the same stream, over that forward's geom_buffer,
+ * image_buffer, binning_buffer (as the forward RETURNED it: a hint repair may have replaced it) and num_rendered; a
+ * no_backward forward's smaller buffers serve as well.  ggr_features_backward runs BEFORE that frame's ggr_backward*: it adds
+ * the feature loss's gradient w.r.t. the 2D mean, conic and opacity into the backward scratch (clearing it first unless
+ * scratch_zeroed = 1, i.e. it was the forward's backward_scratch and nothing has used it since), and the caller then passes
+ * scratch_zeroed = 1 to ggr_backward*, whose own terms meet the feature terms there and which carries the sum on to means3D,
+ * covariance / scale / rotation, opacity and the camera.  dL_dfeatures is overwritten (summed over the views of a set).
+ * `views` NULL: one view (ggr_forward); else the GgrViews of the launch set — only num_views / num_sets are read:
+ * features [P,K] ([B·P,K] with B Gaussian sets, one feature set shared by a set's views), out_features / dL_dout_features
+ * [K,H,W] ([V,K,H,W]).  Features are not examined for non-finite values: like colors_precomp, a NaN feature poisons the
+ * pixels it touches; a Gaussian the forward excluded is in no list and contributes nothing.
+ * Both calls allocate nothing, read nothing back and are hipGraph-capturable.  GGR_E_INVALID, before anything is enqueued,
+ * for a struct_size smaller than the struct, num_features outside 1..GGR_MAX_FEATURES, a nonzero `reserved`, or a NULL
+ * buffer / plane the call needs. */
+#define GGR_MAX_FEATURES 32
+typedef struct GgrFeaturePass {
+    int32_t struct_size;            /* sizeof(GgrFeaturePass) */
+    int32_t num_features;           /* K, 1..GGR_MAX_FEATURES */
+    const float* features;          /* device [P,K] / [B·P,K] */
+    const void* geom_buffer;        /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;     /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;           /* the forward's (−1: sync-free mode) */
+    float* out_features;            /* device [K,H,W] / [V,K,H,W].  forward: OUT.  backward: IN — what the forward wrote */
+    const float* dL_dout_features;  /* backward: device, shape of out_features */
+    float* dL_dfeatures;            /* backward: OUT, shape of features */
+    void* scratch;                  /* backward: the ggr_backward_scratch_bytes(_views) buffer this frame's ggr_backward* gets */
+    int32_t scratch_zeroed;         /* backward: 1 = `scratch` is already clear (GgrBackwardIn.scratch_zeroed's meaning) */
+    int32_t reserved;               /* 0 */
+} GgrFeaturePass;
+
+int ggr_features_forward(const GgrSettings* settings, const GgrViews* views, const GgrFeaturePass* pass, void* stream);
+int ggr_features_backward(const GgrSettings* settings, const GgrViews* views, const GgrFeaturePass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
