@@ -9,7 +9,8 @@ otherwise — INTEGRATION.md §7), silently, exactly as `ggrt_official_amd.splat
 integration paths render the same images.  (`ggrt_official_amd.GaussianRasterizer`, the raw rasterizer, keeps "not chosen
 = bands 0..3 with one warning".)  Upstream's `antialiasing=` keyword of the settings passes through unchanged (False by
 default, as upstream), and so do the `return_alpha=` extension (False: the 3-tuple) and the `features_precomp=` keyword of
-the rasterizer call (None: the tuple as it was).  Nothing else lives here."""
+the rasterizer call (None: the tuple as it was), and the `return_contributions=` extension of the settings (False: the tuple
+as it was).  Nothing else lives here."""
 from ggrt_official_amd import rasterizer as _r
 from ggrt_official_amd.rasterizer import GaussianRasterizationSettings  # noqa: F401
 

@@ -113,6 +113,17 @@ def feature_pass(**fields) -> GgrFeaturePass:
     return GgrFeaturePass(struct_size=C.sizeof(GgrFeaturePass), **fields)
 
 
+class GgrContributionPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
+                ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
+                ("out_weight_sum", C.c_void_p), ("out_weight_max", C.c_void_p), ("out_pixel_count", C.c_void_p)]
+
+
+def contribution_pass(**fields) -> GgrContributionPass:
+    """The argument of ggr_contributions (include/ggr_raster.h), struct_size filled in."""
+    return GgrContributionPass(struct_size=C.sizeof(GgrContributionPass), **fields)
+
+
 FWD_STAGES = ["preprocess", "depth_sort", "tile_count", "tile_scatter", "blend", "colour_side_stream", "tile_sort"]
 DEPTH_SORT = {"auto": 0, "global": 1, "per_tile": 2, "global_3pass": 0x101}
 DEPTH_SORT_NO_BUCKETS = 0x100      # IN flag: never the global sort's bucket form (include/ggr_raster.h)
@@ -163,6 +174,7 @@ SYMBOLS = [
                                          C.POINTER(GgrBackwardIn), C.POINTER(GgrBackwardOut), C.c_void_p]),
     ("ggr_features_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrFeaturePass), C.c_void_p]),
     ("ggr_features_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrFeaturePass), C.c_void_p]),
+    ("ggr_contributions", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrContributionPass), C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),

@@ -7,6 +7,7 @@
 #include "../../include/ggr_raster.h"
 #include "ggr_common.h"
 #include "blend_feat.h"
+#include "blend_contrib.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1057,6 +1058,46 @@ int ggr_features_backward(const GgrSettings* st, const GgrViews* views, const Gg
     ggr::launch_blend_feat_bwd(W, H, im.ranges, (const uint32_t*)fp->binning_buffer, g.splat, fp->features, K, P1, vps,
                                fp->out_features, fp->dL_dout_features, fp->dL_dfeatures, sc.grad2d, V, s);
     KCHECK(st->debug != 0, s, "blend_feat_bwd");
+    return GGR_OK;
+}
+
+// ---- the contribution pass (blend_contrib.hip): per-Gaussian statistics of the blend weight over a forward's lists -------------
+int ggr_contributions(const GgrSettings* st, const GgrViews* views, const GgrContributionPass* cp, void* stream) {
+    g_err[0] = 0;
+    if (!st || !cp) return fail(GGR_E_INVALID, "null settings / contribution pass");
+    if (cp->struct_size < (int32_t)sizeof(GgrContributionPass))
+        return fail(GGR_E_INVALID, "GgrContributionPass.struct_size %d is smaller than the %d bytes of its fields",
+                    (int)cp->struct_size, (int)sizeof(GgrContributionPass));
+    if (cp->reserved != 0) return fail(GGR_E_INVALID, "GgrContributionPass.reserved must be 0, not %d", (int)cp->reserved);
+    if (!cp->out_weight_sum && !cp->out_weight_max && !cp->out_pixel_count)
+        return fail(GGR_E_INVALID, "GgrContributionPass: every output is NULL");
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (!cp->geom_buffer || !cp->image_buffer) return fail(GGR_E_INVALID, "GgrContributionPass: null geom / image buffer of the forward");
+    if (cp->num_rendered != 0 && !cp->binning_buffer) return fail(GGR_E_INVALID, "GgrContributionPass.binning_buffer is NULL");
+    int V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        V = views->num_views;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height;
+    const size_t rows = (size_t)V * (size_t)P1;
+    if (rows == 0) return GGR_OK;
+    if (cp->out_weight_sum) HIP_TRY(hipMemsetAsync(cp->out_weight_sum, 0, rows * sizeof(float), s));
+    if (cp->out_weight_max) HIP_TRY(hipMemsetAsync(cp->out_weight_max, 0, rows * sizeof(float), s));
+    if (cp->out_pixel_count) HIP_TRY(hipMemsetAsync(cp->out_pixel_count, 0, rows * sizeof(int32_t), s));
+    if (cp->num_rendered == 0 || (size_t)W * H == 0) return GGR_OK;   // no list entry anywhere
+    GeomLayout g = ggr_carve_geom((void*)cp->geom_buffer, rows, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)cp->image_buffer, W, H, V);
+    const bool scissored = (st->scissor[0] | st->scissor[1] | st->scissor[2] | st->scissor[3]) != 0;
+    ggr::launch_blend_contrib(W, H, im.ranges, (const uint32_t*)cp->binning_buffer, g.splat, cp->out_weight_sum,
+                              cp->out_weight_max, cp->out_pixel_count, V, scissored ? 1 : 0, s);
+    KCHECK(st->debug != 0, s, "blend_contrib");
     return GGR_OK;
 }
 

@@ -115,4 +115,40 @@ __device__ __forceinline__ void active_box(uint64_t act, float qx0, float qy0, f
     x0 = qx0 + (float)c0; x1 = qx0 + (float)c1; y0 = qy0 + (float)r0; y1 = qy0 + (float)r1;
 }
 
+// ---- the replay passes (blend_feat.hip, blend_contrib.hip): kernels that walk a finished forward's lists again -----------
+// a staged list entry: what the replay needs of the 32-B splat record (the conic pre-multiplied, blend_common.h)
+struct __attribute__((aligned(16))) FeatSplat {
+    float4 a;  // x, y, k·conic.xx, 2k·conic.xy
+    float4 b;  // k·conic.yy, opacity, k·qmax, id (bits)
+};
+
+__device__ __forceinline__ FeatSplat stage_feat_splat(const float4* __restrict__ splat, uint32_t g) {
+    float4 a = splat[2 * (size_t)g];
+    const float4 ge = splat[2 * (size_t)g + 1];
+    float4 b = make_float4(ge.x, ge.y, 0.f, 0.f), c = make_float4(0.f, ge.z, ge.w, 0.f);
+    stage_scale_conic(a, b, c);   // (the same products as the colour blend's staging)
+    FeatSplat r;
+    r.a = a;
+    r.b = make_float4(b.x, b.y, c.z, __uint_as_float(g));
+    return r;
+}
+
+// this wave's survivors of the staged batch: indices into the stage, compacted (blend_fwd.hip's cull, same test)
+__device__ __forceinline__ int cull_batch(const FeatSplat* stage, int nb, uint32_t* my_surv, int lane, float bx0, float by0,
+                                          float bx1, float by1) {
+    int ns = 0;
+    for (int s0 = 0; s0 < nb; s0 += 64) {
+        const int e = s0 + lane;
+        bool keep = false;
+        if (e < nb) {
+            const float4 a = stage[e].a, b = stage[e].b;
+            keep = staged_box_may_contribute(a, b, b.z, bx0, by0, bx1, by1);
+        }
+        const uint64_t mk = __ballot(keep);
+        if (keep) my_surv[ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = (uint32_t)e;
+        ns += __popcll(mk);
+    }
+    return ns;
+}
+
 }  // namespace ggr

@@ -27,44 +27,9 @@ namespace ggr {
 #define BATCH GGR_BATCH
 #define FEAT_GROUP 4   // survivors per trip of the forward's blend loop (one broadcast read of their indices)
 
-// a staged list entry: what the replay needs of the 32-B splat record (the conic pre-multiplied, blend_common.h)
-struct __attribute__((aligned(16))) FeatSplat {
-    float4 a;  // x, y, k·conic.xx, 2k·conic.xy
-    float4 b;  // k·conic.yy, opacity, k·qmax, id (bits)
-};
-
-__device__ __forceinline__ FeatSplat stage_feat_splat(const float4* __restrict__ splat, uint32_t g) {
-    float4 a = splat[2 * (size_t)g];
-    const float4 ge = splat[2 * (size_t)g + 1];
-    float4 b = make_float4(ge.x, ge.y, 0.f, 0.f), c = make_float4(0.f, ge.z, ge.w, 0.f);
-    stage_scale_conic(a, b, c);   // (the same products as the colour blend's staging)
-    FeatSplat r;
-    r.a = a;
-    r.b = make_float4(b.x, b.y, c.z, __uint_as_float(g));
-    return r;
-}
-
 // row of `features` that list id g (pair index view·P1 + Gaussian) reads: Gaussian set view / vps, same Gaussian
 __device__ __forceinline__ size_t feat_row(uint32_t g, int view, int P1, int vps) {
     return (size_t)(view / vps) * (size_t)P1 + (size_t)(g - (uint32_t)view * (uint32_t)P1);
-}
-
-// this wave's survivors of the staged batch: indices into the stage, compacted (blend_fwd.hip's cull, same test)
-__device__ __forceinline__ int cull_batch(const FeatSplat* stage, int nb, uint32_t* my_surv, int lane, float bx0, float by0,
-                                          float bx1, float by1) {
-    int ns = 0;
-    for (int s0 = 0; s0 < nb; s0 += 64) {
-        const int e = s0 + lane;
-        bool keep = false;
-        if (e < nb) {
-            const float4 a = stage[e].a, b = stage[e].b;
-            keep = staged_box_may_contribute(a, b, b.z, bx0, by0, bx1, by1);
-        }
-        const uint64_t mk = __ballot(keep);
-        if (keep) my_surv[ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = (uint32_t)e;
-        ns += __popcll(mk);
-    }
-    return ns;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------

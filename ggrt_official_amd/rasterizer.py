@@ -34,7 +34,7 @@ from torch import nn
 from . import _lib
 
 
-class GaussianRasterizationSettings(NamedTuple):
+class _RasterizationSettingsFields(NamedTuple):
     image_height: int
     image_width: int
     tanfovx: float
@@ -85,6 +85,46 @@ class GaussianRasterizationSettings(NamedTuple):
     return_alpha: bool = False  # extension: also return the accumulated opacity alpha = 1 − T per pixel ([H,W]; [V,H,W] from
     #                         rasterize_views) as a 4th output, differentiable (include/ggr_raster.h GgrForwardExtra) — what
     #                         gsplat returns as `alphas`.  False: the 3-tuple as before, nothing extra allocated or written
+
+class GaussianRasterizationSettings(_RasterizationSettingsFields):
+    """The settings tuple of the fields above — upstream's, then this project's extensions, positional construction and
+    ``_fields`` as they always were — and ONE more setting behind them all that is kept beside the tuple:
+
+    ``return_contributions`` (bool, default False; keyword, or positional behind ``return_alpha``): also return, as the LAST
+    output (behind alpha and features), a ``Contributions(weight_sum, weight_max, pixel_count)`` of [P] tensors ([V,P] from
+    ``rasterize_views``): per Gaussian, over the pixels where the colour blend composited it, Σ w, max w (w = α·T) and the
+    number of those pixels (include/ggr_raster.h GgrContributionPass) — whether a Gaussian was ever SEEN, which ``radii > 0``
+    cannot tell.  Not differentiable.  False: nothing extra allocated or called.  ``_replace`` takes and keeps it; it is not
+    part of the tuple's items (length, iteration, equality and ``_fields`` are those of the fields above)."""
+    return_contributions = False   # (instances made by `_make` from the bare items)
+
+    def __new__(cls, *args, return_contributions=False, **kw):
+        n = len(_RasterizationSettingsFields._fields)
+        if len(args) == n + 1:
+            args, return_contributions = args[:n], args[n]
+        self = super().__new__(cls, *args, **kw)
+        self.return_contributions = bool(return_contributions)
+        return self
+
+    def _replace(self, **kw):
+        on = kw.pop("return_contributions", self.return_contributions)
+        new = super()._replace(**kw)
+        new.return_contributions = bool(on)
+        return new
+
+    def _asdict(self):
+        return dict(super()._asdict(), return_contributions=self.return_contributions)
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", return_contributions={self.return_contributions!r})"
+
+
+class Contributions(NamedTuple):
+    """Per-Gaussian statistics of the blend weight w = α·T over the pixels where the colour blend composited the Gaussian
+    (``return_contributions``): [P] tensors, [V,P] from ``rasterize_views``.  Detached: they carry no gradient."""
+    weight_sum: torch.Tensor    # float32: Σ_pixels w — reproducible up to the order of its float additions
+    weight_max: torch.Tensor    # float32: max_pixels w, 0 if never composited — bit-reproducible
+    pixel_count: torch.Tensor   # int32: pixels where the Gaussian was composited — bit-reproducible
 
 
 class StageProfile:
@@ -176,6 +216,23 @@ def _features_forward(lib, st, vw, feat, geom, img, binb, num_rendered, out, str
                            image_buffer=img.data_ptr(), binning_buffer=_ptr(binb), num_rendered=int(num_rendered),
                            out_features=out.data_ptr())
     _check(lib.ggr_features_forward(C.byref(st), _byref(vw), C.byref(fp), stream), "ggr_features_forward")
+
+
+def _contributions(lib, st, vw, geom, img, binb, num_rendered, shape, dev, stream):
+    """ggr_contributions over the buffers of the forward that has just returned: the three arrays of `shape` ([P] / [V,P])."""
+    ws = torch.empty(shape, dtype=torch.float32, device=dev)
+    wm = torch.empty(shape, dtype=torch.float32, device=dev)
+    pc = torch.empty(shape, dtype=torch.int32, device=dev)
+    cp = _lib.contribution_pass(reserved=0, geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
+                                num_rendered=int(num_rendered), out_weight_sum=ws.data_ptr(), out_weight_max=wm.data_ptr(),
+                                out_pixel_count=pc.data_ptr())
+    _check(lib.ggr_contributions(C.byref(st), _byref(vw), C.byref(cp), stream), "ggr_contributions")
+    return ws, wm, pc
+
+
+def _with_contributions(out, on: bool):
+    """The public tuple: the three trailing arrays of a `return_contributions` call as ONE `Contributions` element, last."""
+    return out[:-3] + (Contributions(*out[-3:]),) if on else out
 
 
 def _features_backward(lib, st, vw, feat, geom, img, binb, num_rendered, out, grad_out, d_feat, scratch, zeroed, stream):
@@ -533,6 +590,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             if feat_c is not None:   # K feature channels over the lists this forward has just built (csrc/blend_feat.hip)
                 feat_out = torch.empty((feat_c.shape[1], H, W), dtype=torch.float32, device=dev)
                 _features_forward(lib, st, None, feat_c, geom, img, holder.get("bin"), fout.num_rendered, feat_out, stream)
+            want_contrib = bool(getattr(rs, "return_contributions", False))
+            contrib = ()
+            if want_contrib:   # per-Gaussian statistics of the weights this forward has just blended (csrc/blend_contrib.hip)
+                contrib = _contributions(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, (P,), dev, stream)
 
         # exact mode: count known, nothing to keep.  Sync-free mode: count + flags live in the geometry buffer on the
         # device, so that (≈100 MB at P = 1 M) buffer stays referenced until this thread's next forward
@@ -551,7 +612,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape)
         out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
-        return out + (feat_out,) if feat_c is not None else out
+        if feat_c is not None:
+            out += (feat_out,)
+        if want_contrib:   # (three plain arrays behind everything differentiable; the callers below wrap them)
+            ctx.mark_non_differentiable(radii, *contrib)
+            out += contrib
+        return out
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, *grad_extra):
@@ -561,7 +627,7 @@ class _RasterizeGaussians(torch.autograd.Function):
          feat_out) = ctx.saved_tensors
         want_alpha, has_feat, feat_shape = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
-        grad_feat = grad_extra[-1] if has_feat else None
+        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' None)
         P, M, H, W = ctx.dims
         dev = means3D.device
         need_pose = any(ctx.needs_input_grad[8:11])
@@ -745,6 +811,10 @@ class _RasterizeViews(torch.autograd.Function):
             if feat_c is not None:
                 feat_out = torch.empty((V, feat_c.shape[1], H, W), dtype=torch.float32, device=dev)
                 _features_forward(lib, st, vw, feat_c, geom, img, holder.get("bin"), fout.num_rendered, feat_out, stream)
+            want_contrib = bool(getattr(rs, "return_contributions", False))
+            contrib = ()
+            if want_contrib:
+                contrib = _contributions(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, (V, P), dev, stream)
         _tls.last_forward = (geom, P * V) if capacity > 0 else (None, int(fout.num_rendered))
         _tls.last_binning = (int(fout.depth_sort_used), int(fout.max_list_len))
         ctx.raster_settings = rs
@@ -762,7 +832,12 @@ class _RasterizeViews(torch.autograd.Function):
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape)
         out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
-        return out + (feat_out,) if feat_c is not None else out
+        if feat_c is not None:
+            out += (feat_out,)
+        if want_contrib:   # (three plain arrays behind everything differentiable; the callers below wrap them)
+            ctx.mark_non_differentiable(radii, *contrib)
+            out += contrib
+        return out
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, *grad_extra):
@@ -772,7 +847,7 @@ class _RasterizeViews(torch.autograd.Function):
          fwd_scratch, feat, feat_out) = ctx.saved_tensors
         want_alpha, has_feat, feat_shape = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
-        grad_feat = grad_extra[-1] if has_feat else None
+        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' None)
         P, M, H, W, V, B = ctx.dims
         PT = P * B   # rows of the flat [B·P, …] gradient arrays
         dev = means3D.device
@@ -863,7 +938,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     the views, per-view results equal ``GaussianRasterizer``'s (same lists, bit-identical images).
     ``features_precomp [P,K]`` (``[B,P,K]`` with Gaussian sets; 1 <= K <= 32): K more per-Gaussian channels composited in
     one pass over the same lists — ``features [V,K,H,W]`` (Σ f·α·T, no background) is then appended as the LAST output,
-    differentiable like the colour."""
+    differentiable like the colour.  With ``raster_settings.return_contributions`` a ``Contributions`` of ``[V,P]`` tensors
+    (Σ w, max w, pixel count per view and Gaussian; not differentiable) follows as the very last output."""
     shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
     scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
     if (shs is None) == (colors_precomp is None):
@@ -871,9 +947,10 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     if ((scales is None or rotations is None) and cov3D_precomp is None) or (
             (scales is not None or rotations is not None) and cov3D_precomp is not None):
         raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-    return _RasterizeViews.apply(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                 viewmatrices, projmatrices, campos, aux_precomp, means2D, raster_settings, bg, tanfov,
-                                 input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))
+    out = _RasterizeViews.apply(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                viewmatrices, projmatrices, campos, aux_precomp, means2D, raster_settings, bg, tanfov,
+                                input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))
+    return _with_contributions(out, bool(getattr(raster_settings, "return_contributions", False)))
 
 
 def camera_setup(extrinsics: torch.Tensor, intrinsics: torch.Tensor, near: torch.Tensor, far: torch.Tensor,
@@ -942,9 +1019,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         raster_settings, aux_precomp=None, features_precomp=None):
     """Function form, argument order of upstream's ``rasterize_gaussians`` (+ the optional aux feature and feature channels)."""
     rs = raster_settings
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
-                                     torch.is_grad_enabled(), _none_if_empty(features_precomp))
+    out = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                    cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
+                                    torch.is_grad_enabled(), _none_if_empty(features_precomp))
+    return _with_contributions(out, bool(getattr(rs, "return_contributions", False)))
 
 
 class GaussianRasterizer(nn.Module):
@@ -978,7 +1056,9 @@ class GaussianRasterizer(nn.Module):
         return value then is Σ aux·α·T instead of Σ z·α·T (one rasterization serves GGRt's colour AND depth
         pass — see ``splatting.render_color_and_depth``).  ``features_precomp`` [P,K] (extension, optional, 1 <= K <= 32):
         K more per-Gaussian channels rendered in ONE pass over the lists of this call — the returned tuple then grows by
-        ``features [K,H,W]`` = Σ f·α·T (no background term) as its LAST element, differentiable."""
+        ``features [K,H,W]`` = Σ f·α·T (no background term) as its LAST element, differentiable.  With
+        ``return_contributions=True`` in the settings a ``Contributions(weight_sum, weight_max, pixel_count)`` of [P] tensors
+        follows behind everything else (not differentiable)."""
         shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
         scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):

@@ -450,6 +450,43 @@ typedef struct GgrFeaturePass {
 int ggr_features_forward(const GgrSettings* settings, const GgrViews* views, const GgrFeaturePass* pass, void* stream);
 int ggr_features_backward(const GgrSettings* settings, const GgrViews* views, const GgrFeaturePass* pass, void* stream);
 
+/* ---- the contribution pass: per-Gaussian statistics of the blend weight over a forward's lists (ABI 11, additive) ------------
+ * Per (view v, Gaussian g), over the pixels where the Gaussian's list entry is LIVE — composited by the colour blend of that
+ * forward: power <= 0, α >= 1/255 after the 0.99 cap, and in front of the entry that would take T below 1e-4 — with
+ * w = α·T the colour's own weight (the same α — the compensated opacity's under antialiasing —, T and arithmetic, bit for bit):
+ *     out_weight_sum  [P] / [V,P] float32   Σ_pixels w        (LightGaussian's summed blend weight)
+ *     out_weight_max  [P] / [V,P] float32   max_pixels w      (RadSplat's maximum blend weight; 0 if never live)
+ *     out_pixel_count [P] / [V,P] int32     the number of those pixels (gsplat-style visibility)
+ * A Gaussian with radii == 0, one excluded by the non-finite contract at the top of this file, and one listed only in tiles
+ * outside the scissor window (those tiles have no list entries) have zeros in all three.  `radii > 0` says that a Gaussian's
+ * box touched the frustum; these say whether it was ever seen: one behind an opaque surface has radii > 0 and zeros here.
+ * Forward only: the arrays are not differentiable.
+ *
+ * Protocol, as ggr_features_forward: ggr_contributions runs AFTER ggr_forward* (any variant, any mode) on the same stream, over
+ * that forward's geom_buffer, image_buffer, binning_buffer (as the forward RETURNED it: a hint repair may have replaced it) and
+ * num_rendered; a no_backward forward's smaller buffers serve as well (the pass applies the stop rule itself and reads nothing a
+ * training forward stores for its backward).  `views` NULL: one view (ggr_forward); else the GgrViews of the launch set — only
+ * num_views / num_sets are read.  The call clears the requested outputs itself, on the stream; it allocates nothing, reads
+ * nothing back and is hipGraph-capturable.  Each output may be NULL (not computed), at least one must not be.
+ * Reproducibility: out_weight_max and out_pixel_count are integer atomics of order-independent values — bit-identical from
+ * run to run; out_weight_sum is a float sum added atomically — reproducible only up to the order of its additions.
+ * GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero `reserved`, all three
+ * outputs NULL, or a NULL buffer the call needs. */
+typedef struct GgrContributionPass {
+    int32_t struct_size;            /* sizeof(GgrContributionPass) */
+    int32_t reserved;               /* 0 */
+    const void* geom_buffer;        /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;     /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;           /* the forward's (−1: sync-free mode) */
+    float* out_weight_sum;          /* device [P] / [V,P] or NULL */
+    float* out_weight_max;          /* device [P] / [V,P] or NULL */
+    int32_t* out_pixel_count;       /* device [P] / [V,P] or NULL */
+} GgrContributionPass;
+
+int ggr_contributions(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrContributionPass* pass,
+                      void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
