@@ -8,6 +8,7 @@
 #include "ggr_common.h"
 #include "blend_feat.h"
 #include "blend_contrib.h"
+#include "blend_pick.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1098,6 +1099,50 @@ int ggr_contributions(const GgrSettings* st, const GgrViews* views, const GgrCon
     ggr::launch_blend_contrib(W, H, im.ranges, (const uint32_t*)cp->binning_buffer, g.splat, cp->out_weight_sum,
                               cp->out_weight_max, cp->out_pixel_count, V, scissored ? 1 : 0, s);
     KCHECK(st->debug != 0, s, "blend_contrib");
+    return GGR_OK;
+}
+
+// ---- the pick pass (blend_pick.hip): per-pixel median-depth Gaussian, dominant Gaussian and contributor count -----------------
+int ggr_pixel_picks(const GgrSettings* st, const GgrViews* views, const GgrPickPass* pp, void* stream) {
+    g_err[0] = 0;
+    if (!st || !pp) return fail(GGR_E_INVALID, "null settings / pick pass");
+    if (pp->struct_size < (int32_t)sizeof(GgrPickPass))
+        return fail(GGR_E_INVALID, "GgrPickPass.struct_size %d is smaller than the %d bytes of its fields", (int)pp->struct_size,
+                    (int)sizeof(GgrPickPass));
+    if (pp->reserved != 0) return fail(GGR_E_INVALID, "GgrPickPass.reserved must be 0, not %d", (int)pp->reserved);
+    if (!pp->out_median_index && !pp->out_median_depth && !pp->out_max_index && !pp->out_max_weight && !pp->out_count)
+        return fail(GGR_E_INVALID, "GgrPickPass: every output is NULL");
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (!pp->geom_buffer || !pp->image_buffer) return fail(GGR_E_INVALID, "GgrPickPass: null geom / image buffer of the forward");
+    if (pp->num_rendered != 0 && !pp->binning_buffer) return fail(GGR_E_INVALID, "GgrPickPass.binning_buffer is NULL");
+    int V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        V = views->num_views;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height;
+    const size_t pixels = (size_t)V * (size_t)W * (size_t)H;
+    if (pixels == 0) return GGR_OK;
+    if (P1 == 0 || pp->num_rendered == 0) {   // no list entry anywhere: every pixel gets the "none" values (−1 = all bits set)
+        if (pp->out_median_index) HIP_TRY(hipMemsetAsync(pp->out_median_index, 0xFF, pixels * sizeof(int32_t), s));
+        if (pp->out_median_depth) HIP_TRY(hipMemsetAsync(pp->out_median_depth, 0, pixels * sizeof(float), s));
+        if (pp->out_max_index) HIP_TRY(hipMemsetAsync(pp->out_max_index, 0xFF, pixels * sizeof(int32_t), s));
+        if (pp->out_max_weight) HIP_TRY(hipMemsetAsync(pp->out_max_weight, 0, pixels * sizeof(float), s));
+        if (pp->out_count) HIP_TRY(hipMemsetAsync(pp->out_count, 0, pixels * sizeof(int32_t), s));
+        return GGR_OK;
+    }
+    GeomLayout g = ggr_carve_geom((void*)pp->geom_buffer, (size_t)V * (size_t)P1, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)pp->image_buffer, W, H, V);
+    const bool scissored = (st->scissor[0] | st->scissor[1] | st->scissor[2] | st->scissor[3]) != 0;
+    ggr::launch_blend_pick(W, H, im.ranges, (const uint32_t*)pp->binning_buffer, g.splat, pp->out_median_index,
+                           pp->out_median_depth, pp->out_max_index, pp->out_max_weight, pp->out_count, V, P1, scissored ? 1 : 0, s);
+    KCHECK(st->debug != 0, s, "blend_pick");
     return GGR_OK;
 }
 

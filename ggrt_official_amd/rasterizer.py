@@ -95,28 +95,43 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
     ``rasterize_views``): per Gaussian, over the pixels where the colour blend composited it, Σ w, max w (w = α·T) and the
     number of those pixels (include/ggr_raster.h GgrContributionPass) — whether a Gaussian was ever SEEN, which ``radii > 0``
     cannot tell.  Not differentiable.  False: nothing extra allocated or called.  ``_replace`` takes and keeps it; it is not
-    part of the tuple's items (length, iteration, equality and ``_fields`` are those of the fields above)."""
-    return_contributions = False   # (instances made by `_make` from the bare items)
+    part of the tuple's items (length, iteration, equality and ``_fields`` are those of the fields above).
 
-    def __new__(cls, *args, return_contributions=False, **kw):
+    ``return_picks`` (bool, default False; keyword, or positional behind ``return_contributions``), kept beside the tuple in
+    the same way: also return, as the VERY LAST output (behind the contributions), a ``PixelPicks(median_depth, median_index,
+    max_weight, max_index, count)`` of [H,W] planes ([V,H,W] from ``rasterize_views``): per pixel, over the entries the colour
+    blend composited there, the Gaussian at which the transmittance crosses 1/2 and its depth value, the Gaussian of the
+    largest blend weight and that weight, and the number of composited entries (include/ggr_raster.h GgrPickPass).  Not
+    differentiable — ``pick_values`` gathers a differentiable per-Gaussian value at an index plane.  False: nothing extra
+    allocated or called."""
+    return_contributions = False   # (instances made by `_make` from the bare items)
+    return_picks = False
+
+    def __new__(cls, *args, return_contributions=False, return_picks=False, **kw):
         n = len(_RasterizationSettingsFields._fields)
-        if len(args) == n + 1:
+        if len(args) == n + 2:
+            args, return_contributions, return_picks = args[:n], args[n], args[n + 1]
+        elif len(args) == n + 1:
             args, return_contributions = args[:n], args[n]
         self = super().__new__(cls, *args, **kw)
         self.return_contributions = bool(return_contributions)
+        self.return_picks = bool(return_picks)
         return self
 
     def _replace(self, **kw):
         on = kw.pop("return_contributions", self.return_contributions)
+        picks = kw.pop("return_picks", self.return_picks)
         new = super()._replace(**kw)
         new.return_contributions = bool(on)
+        new.return_picks = bool(picks)
         return new
 
     def _asdict(self):
-        return dict(super()._asdict(), return_contributions=self.return_contributions)
+        return dict(super()._asdict(), return_contributions=self.return_contributions, return_picks=self.return_picks)
 
     def __repr__(self):
-        return super().__repr__()[:-1] + f", return_contributions={self.return_contributions!r})"
+        return (super().__repr__()[:-1] + f", return_contributions={self.return_contributions!r}"
+                f", return_picks={self.return_picks!r})")
 
 
 class Contributions(NamedTuple):
@@ -125,6 +140,33 @@ class Contributions(NamedTuple):
     weight_sum: torch.Tensor    # float32: Σ_pixels w — reproducible up to the order of its float additions
     weight_max: torch.Tensor    # float32: max_pixels w, 0 if never composited — bit-reproducible
     pixel_count: torch.Tensor   # int32: pixels where the Gaussian was composited — bit-reproducible
+
+
+class PixelPicks(NamedTuple):
+    """Per-pixel picks over the list entries the colour blend composited at the pixel (``return_picks``): [H,W] planes, [V,H,W]
+    from ``rasterize_views``.  Indices are Gaussian indices in [0,P) within the view's Gaussian set, −1 where the pixel composited
+    nothing (the float planes are 0 there).  Detached: they carry no gradient (``pick_values``).  All bit-reproducible."""
+    median_depth: torch.Tensor   # float32: the depth value (what the depth plane blends) of the median Gaussian
+    median_index: torch.Tensor   # int32: the last composited Gaussian in front of which the transmittance is still > 1/2
+    max_weight: torch.Tensor     # float32: the largest blend weight w = α·T at the pixel
+    max_index: torch.Tensor      # int32: the Gaussian of that weight (the earliest in depth order among equals)
+    count: torch.Tensor          # int32: the number of composited entries
+
+
+def pick_values(values: torch.Tensor, index: torch.Tensor, fill: float = 0.0) -> torch.Tensor:
+    """Per-Gaussian ``values`` ([P] or [P,C]) gathered at an index plane of ``PixelPicks`` (any shape, −1 = no Gaussian): the
+    result has the plane's shape (+ [C]) and holds ``fill`` where the index is −1.  Differentiable in ``values`` — the way to a
+    gradient through the median depth: ``pick_values(view_z, picks.median_index)`` with the per-Gaussian depth computed in
+    torch (or ``aux_precomp`` itself).  Pure torch; works on CPU tensors.  For the [V,H,W] planes of a launch set call it per
+    view (per Gaussian set)."""
+    if values.dim() not in (1, 2):
+        raise ValueError(f"pick_values: values must be [P] or [P,C], not {tuple(values.shape)}")
+    idx = index.to(device=values.device, dtype=torch.long)
+    valid = idx >= 0
+    got = values[idx.clamp(min=0)]
+    if values.dim() == 2:
+        valid = valid.unsqueeze(-1)
+    return torch.where(valid, got, torch.full((), fill, dtype=values.dtype, device=values.device))
 
 
 class StageProfile:
@@ -230,9 +272,28 @@ def _contributions(lib, st, vw, geom, img, binb, num_rendered, shape, dev, strea
     return ws, wm, pc
 
 
-def _with_contributions(out, on: bool):
-    """The public tuple: the three trailing arrays of a `return_contributions` call as ONE `Contributions` element, last."""
-    return out[:-3] + (Contributions(*out[-3:]),) if on else out
+def _pixel_picks(lib, st, vw, geom, img, binb, num_rendered, shape, dev, stream):
+    """ggr_pixel_picks over the buffers of the forward that has just returned: the five planes of `shape` ([H,W] / [V,H,W]), in
+    `PixelPicks`' order.  The call writes every element."""
+    f = lambda: torch.empty(shape, dtype=torch.float32, device=dev)
+    i = lambda: torch.empty(shape, dtype=torch.int32, device=dev)
+    md, mi, xw, xi, cnt = f(), i(), f(), i(), i()
+    pp = _lib.pick_pass(reserved=0, geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
+                        num_rendered=int(num_rendered), out_median_index=mi.data_ptr(), out_median_depth=md.data_ptr(),
+                        out_max_index=xi.data_ptr(), out_max_weight=xw.data_ptr(), out_count=cnt.data_ptr())
+    _check(lib.ggr_pixel_picks(C.byref(st), _byref(vw), C.byref(pp), stream), "ggr_pixel_picks")
+    return md, mi, xw, xi, cnt
+
+
+def _with_contributions(out, on: bool, picks: bool = False):
+    """The public tuple: the three trailing arrays of a `return_contributions` call as ONE `Contributions` element — and the
+    five planes of a `return_picks` call, behind them, as ONE `PixelPicks` element, last."""
+    tail = ()
+    if picks:
+        out, tail = out[:-5], (PixelPicks(*out[-5:]),)
+    if on:
+        out = out[:-3] + (Contributions(*out[-3:]),)
+    return out + tail
 
 
 def _features_backward(lib, st, vw, feat, geom, img, binb, num_rendered, out, grad_out, d_feat, scratch, zeroed, stream):
@@ -594,6 +655,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             contrib = ()
             if want_contrib:   # per-Gaussian statistics of the weights this forward has just blended (csrc/blend_contrib.hip)
                 contrib = _contributions(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, (P,), dev, stream)
+            picks = ()
+            if bool(getattr(rs, "return_picks", False)):   # per-pixel picks over the same lists (csrc/blend_pick.hip)
+                picks = _pixel_picks(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, (H, W), dev, stream)
 
         # exact mode: count known, nothing to keep.  Sync-free mode: count + flags live in the geometry buffer on the
         # device, so that (≈100 MB at P = 1 M) buffer stays referenced until this thread's next forward
@@ -614,9 +678,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
         if feat_c is not None:
             out += (feat_out,)
-        if want_contrib:   # (three plain arrays behind everything differentiable; the callers below wrap them)
-            ctx.mark_non_differentiable(radii, *contrib)
-            out += contrib
+        if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
+            ctx.mark_non_differentiable(radii, *contrib, *picks)
+            out += contrib + picks
         return out
 
     @staticmethod
@@ -627,7 +691,7 @@ class _RasterizeGaussians(torch.autograd.Function):
          feat_out) = ctx.saved_tensors
         want_alpha, has_feat, feat_shape = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
-        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' None)
+        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' and picks' None)
         P, M, H, W = ctx.dims
         dev = means3D.device
         need_pose = any(ctx.needs_input_grad[8:11])
@@ -815,6 +879,9 @@ class _RasterizeViews(torch.autograd.Function):
             contrib = ()
             if want_contrib:
                 contrib = _contributions(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, (V, P), dev, stream)
+            picks = ()
+            if bool(getattr(rs, "return_picks", False)):
+                picks = _pixel_picks(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, (V, H, W), dev, stream)
         _tls.last_forward = (geom, P * V) if capacity > 0 else (None, int(fout.num_rendered))
         _tls.last_binning = (int(fout.depth_sort_used), int(fout.max_list_len))
         ctx.raster_settings = rs
@@ -834,9 +901,9 @@ class _RasterizeViews(torch.autograd.Function):
         out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
         if feat_c is not None:
             out += (feat_out,)
-        if want_contrib:   # (three plain arrays behind everything differentiable; the callers below wrap them)
-            ctx.mark_non_differentiable(radii, *contrib)
-            out += contrib
+        if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
+            ctx.mark_non_differentiable(radii, *contrib, *picks)
+            out += contrib + picks
         return out
 
     @staticmethod
@@ -847,7 +914,7 @@ class _RasterizeViews(torch.autograd.Function):
          fwd_scratch, feat, feat_out) = ctx.saved_tensors
         want_alpha, has_feat, feat_shape = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
-        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' None)
+        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' and picks' None)
         P, M, H, W, V, B = ctx.dims
         PT = P * B   # rows of the flat [B·P, …] gradient arrays
         dev = means3D.device
@@ -939,7 +1006,9 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     ``features_precomp [P,K]`` (``[B,P,K]`` with Gaussian sets; 1 <= K <= 32): K more per-Gaussian channels composited in
     one pass over the same lists — ``features [V,K,H,W]`` (Σ f·α·T, no background) is then appended as the LAST output,
     differentiable like the colour.  With ``raster_settings.return_contributions`` a ``Contributions`` of ``[V,P]`` tensors
-    (Σ w, max w, pixel count per view and Gaussian; not differentiable) follows as the very last output."""
+    (Σ w, max w, pixel count per view and Gaussian; not differentiable) follows, and with ``raster_settings.return_picks`` a
+    ``PixelPicks`` of ``[V,H,W]`` planes (median depth / index, dominant weight / index, contributor count per pixel; indices
+    within the view's Gaussian set; not differentiable) is the very last output."""
     shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
     scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
     if (shs is None) == (colors_precomp is None):
@@ -950,7 +1019,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     out = _RasterizeViews.apply(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                 viewmatrices, projmatrices, campos, aux_precomp, means2D, raster_settings, bg, tanfov,
                                 input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))
-    return _with_contributions(out, bool(getattr(raster_settings, "return_contributions", False)))
+    return _with_contributions(out, bool(getattr(raster_settings, "return_contributions", False)),
+                               bool(getattr(raster_settings, "return_picks", False)))
 
 
 def camera_setup(extrinsics: torch.Tensor, intrinsics: torch.Tensor, near: torch.Tensor, far: torch.Tensor,
@@ -1022,7 +1092,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     out = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                     cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
                                     torch.is_grad_enabled(), _none_if_empty(features_precomp))
-    return _with_contributions(out, bool(getattr(rs, "return_contributions", False)))
+    return _with_contributions(out, bool(getattr(rs, "return_contributions", False)), bool(getattr(rs, "return_picks", False)))
 
 
 class GaussianRasterizer(nn.Module):
@@ -1058,7 +1128,8 @@ class GaussianRasterizer(nn.Module):
         K more per-Gaussian channels rendered in ONE pass over the lists of this call — the returned tuple then grows by
         ``features [K,H,W]`` = Σ f·α·T (no background term) as its LAST element, differentiable.  With
         ``return_contributions=True`` in the settings a ``Contributions(weight_sum, weight_max, pixel_count)`` of [P] tensors
-        follows behind everything else (not differentiable)."""
+        follows behind everything else (not differentiable), and with ``return_picks=True`` a ``PixelPicks(median_depth,
+        median_index, max_weight, max_index, count)`` of [H,W] planes behind that (not differentiable; ``pick_values``)."""
         shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
         scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):

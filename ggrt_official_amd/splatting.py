@@ -35,7 +35,7 @@ from typing import Literal, Optional
 import torch
 from torch import Tensor, nn
 
-from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer
+from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelPicks
 
 DepthRenderingMode = Literal["depth", "disparity", "relative_disparity", "log"]
 
@@ -86,6 +86,7 @@ class DecoderOutput:
     alpha: Optional[Tensor] = None  # [b, v, h, w]: accumulated opacity 1 − T (DecoderSplattingCUDA(..., return_alpha=True))
     features: Optional[Tensor] = None  # [b, v, K, h, w]: Σ f·α·T of the per-Gaussian channels (…, gaussian_features=[b,g,K])
     contributions: Optional[Contributions] = None  # [b, v, g] tensors: Σ w, max w, pixel count (…, return_contributions=True)
+    picks: Optional[PixelPicks] = None  # [b, v, h, w] planes: median depth / index, dominant weight / index, count (…, return_picks=True)
 
 
 def get_fov(intrinsics: Tensor) -> Tensor:
@@ -173,7 +174,7 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,
-                       antialiasing=False, return_alpha=False, return_contributions=False):
+                       antialiasing=False, return_alpha=False, *, return_picks=False, return_contributions=False):
     """Everything ``render_cuda`` hands to the rasterizer, batched: a list of
     (GaussianRasterizationSettings, kwargs) per view.  Split out so the golden-vector tests can
     compare it with what the reference's call site produces.
@@ -220,7 +221,8 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
             sh_degree=degree, campos=extrinsics[i, :3, 3], prefiltered=False,
             sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}),
             **({"antialiasing": True} if antialiasing else {}), **({"return_alpha": True} if return_alpha else {}),
-            **({"return_contributions": True} if return_contributions else {}))
+            **({"return_contributions": True} if return_contributions else {}),
+            **({"return_picks": True} if return_picks else {}))
         kwargs = dict(means3D=gaussian_means[i], shs=shs[i] if use_sh else None,
                       colors_precomp=None if use_sh else shs[i, :, 0, :],
                       opacities=gaussian_opacities[i, ..., None])
@@ -251,6 +253,17 @@ def _rasterize_views(calls, aux=None, features=None):
     return outs
 
 
+def _stack_picks(ps) -> PixelPicks:
+    """Per-call `PixelPicks` ([h,w] or [v,h,w] planes) → one with a leading axis over the calls"""
+    return PixelPicks(*(torch.stack([getattr(p, f) for p in ps]) for f in PixelPicks._fields))
+
+
+def _tail_index(want_contrib: bool, want_picks: bool):
+    """Where a rasterizer call's tuple has (the rendered features, the Contributions): the picks, when on, are its last
+    element, the contributions stand in front of them, the features in front of both"""
+    return -1 - int(want_contrib) - int(want_picks), -1 - int(want_picks)
+
+
 def _stack_contributions(cs) -> Contributions:
     """Per-call `Contributions` ([g] or [v,g] tensors) → one with a leading axis over the calls"""
     return Contributions(*(torch.stack([getattr(c, f) for c in cs]) for f in Contributions._fields))
@@ -261,7 +274,7 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
                 scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                gaussian_features: Optional[Tensor] = None, return_contributions: bool = False):
+                gaussian_features: Optional[Tensor] = None, *, return_picks: bool = False, return_contributions: bool = False):
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
 
@@ -278,19 +291,25 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     lists; the result becomes a tuple whose LAST element is ``features [batch,K,h,w]`` (Σ f·α·T, no background).
 
     ``return_contributions=True`` (extension): the result becomes a tuple that ends — behind alpha and features — with a
-    ``Contributions`` of ``[batch,g]`` tensors: per view and Gaussian Σ w, max w and the pixel count of the same pass."""
+    ``Contributions`` of ``[batch,g]`` tensors: per view and Gaussian Σ w, max w and the pixel count of the same pass.
+
+    ``return_picks=True`` (extension; keyword-only): the tuple's VERY LAST element is a ``PixelPicks`` of ``[batch,h,w]``
+    planes: per pixel the median depth / index, the dominant weight / index and the contributor count of the same pass."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing,
-                               return_alpha, return_contributions)
+                               return_alpha, return_picks=return_picks, return_contributions=return_contributions)
     outs = _rasterize_views(calls, features=gaussian_features)
+    fi, ci = _tail_index(return_contributions, return_picks)
     res = (torch.stack([o[0] for o in outs]),)
     if return_alpha:
         res += (torch.stack([o[3] for o in outs]),)
     if gaussian_features is not None:
-        res += (torch.stack([o[-2 if return_contributions else -1] for o in outs]),)
+        res += (torch.stack([o[fi] for o in outs]),)
     if return_contributions:
-        res += (_stack_contributions([o[-1] for o in outs]),)
+        res += (_stack_contributions([o[ci] for o in outs]),)
+    if return_picks:
+        res += (_stack_picks([o[-1] for o in outs]),)
     return res if len(res) > 1 else res[0]
 
 
@@ -336,7 +355,8 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
                            gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
                            antialiasing: bool = False, return_alpha: bool = False,
-                           gaussian_features: Optional[Tensor] = None, return_contributions: bool = False):
+                           gaussian_features: Optional[Tensor] = None, *, return_picks: bool = False,
+                           return_contributions: bool = False):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
 
@@ -347,19 +367,23 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     SAME pass: identical values and gradients, half the work.  Returns ([b,3,h,w], [b,h,w]) — and the accumulated opacity
     [b,h,w] of the same pass as a third result with ``return_alpha=True``; with ``gaussian_features [b,g,K]`` the rendered
     ``features [b,K,h,w]`` of the same pass as the LAST result; with ``return_contributions=True`` a ``Contributions`` of
-    ``[b,g]`` tensors behind everything else."""
+    ``[b,g]`` tensors behind everything else — except a ``PixelPicks`` of ``[b,h,w]`` planes, the very last result with
+    ``return_picks=True`` (keyword-only; its ``median_depth`` holds the depth pass's per-Gaussian value ``max(0.5 + C0·f(z), 0)``)."""
     feat = depth_feature(extrinsics, gaussian_means, near, far, depth_mode)  # unscaled, as the reference
     aux = (0.5 + SH_C0 * feat).clamp(min=0.0)
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing, return_alpha,
-                               return_contributions)
+                               return_picks=return_picks, return_contributions=return_contributions)
     outs = _rasterize_views(calls, aux=aux, features=gaussian_features)
-    picks = (0, 2, 3) if return_alpha else (0, 2)
+    fi, ci = _tail_index(return_contributions, return_picks)
+    planes = (0, 2, 3) if return_alpha else (0, 2)
     if gaussian_features is not None:
-        picks += (-2 if return_contributions else -1,)
-    res = tuple(torch.stack([o[k] for o in outs]) for k in picks)
-    return res + (_stack_contributions([o[-1] for o in outs]),) if return_contributions else res
+        planes += (fi,)
+    res = tuple(torch.stack([o[k] for o in outs]) for k in planes)
+    if return_contributions:
+        res += (_stack_contributions([o[ci] for o in outs]),)
+    return res + (_stack_picks([o[-1] for o in outs]),) if return_picks else res
 
 
 def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape,
@@ -367,7 +391,8 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
                        sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                       gaussian_features: Optional[Tensor] = None, return_contributions: bool = False):
+                       gaussian_features: Optional[Tensor] = None, *, return_picks: bool = False,
+                       return_contributions: bool = False):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
     * ``device_camera``: view / projection matrices, camera position, tan(fov/2) and 1/near of all views come
@@ -393,11 +418,13 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     opacity 1 − T of the same launches (differentiable); with ``gaussian_features [b,g,K]`` (one feature set per batch
     element, shared by its views) also ``features [n,K,h,w]``, rendered through the same launch sets, as the LAST result;
     with ``return_contributions=True`` a ``Contributions`` of ``[n,g]`` tensors (per view and Gaussian Σ w, max w, pixel
-    count of the same launch sets; not differentiable) behind everything else."""
+    count of the same launch sets; not differentiable) behind everything else — except, with ``return_picks=True`` (keyword-only),
+    a ``PixelPicks`` of ``[n,h,w]`` planes (per pixel the median depth / index, the dominant weight / index and the contributor
+    count of the same launch sets; indices within the view's batch element; not differentiable), the very last result."""
     n = extrinsics.shape[0]
     has_feat = gaussian_features is not None
-    want_contrib = bool(return_contributions)
-    fi = -2 if want_contrib else -1   # where a rasterizer call's tuple has the rendered features
+    want_contrib, want_picks = bool(return_contributions), bool(return_picks)
+    fi, ci = _tail_index(want_contrib, want_picks)   # where a rasterizer call's tuple has the rendered features / contributions
     h, w = image_shape
     d_sh = gaussians.harmonics.shape[-1]
     degree = isqrt(d_sh) - 1
@@ -447,14 +474,15 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[0], projmatrix=full[0], sh_degree=degree, campos=campos[0], prefiltered=False,
             list_capacity=list_capacity * n, sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks)
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
         out = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
                               settings, shs=gaussians.harmonics, aux_precomp=aux, input_scale=scale,
                               features_precomp=gaussian_features, **kw)
         return _fused_result(out[0], out[2] if depth_mode is not None else None, out[3] if return_alpha else None,
-                             return_alpha, out[fi] if has_feat else None, out[-1] if want_contrib else None)
+                             return_alpha, out[fi] if has_feat else None, out[ci] if want_contrib else None,
+                                 out[-1] if want_picks else None)
     # batch element b of every Gaussian tensor WITHOUT `t[b]`: select's backward zero-fills a full [B,…] tensor
     # and copies the slice in, per view (0.2 ms per view for 1 M × 25 SH coefficients).  One unbind per tensor
     # (backward = one stack) — or a free reshape when there is a single batch element, GGRt's case.
@@ -465,7 +493,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     g_means, g_cov, g_sh, g_op = (per_batch(gaussians.means), per_batch(gaussians.covariances),
                                   per_batch(gaussians.harmonics), per_batch(gaussians.opacities))
     g_scales, g_rot, g_feat = per_batch(gaussians.scales), per_batch(gaussians.rotations), per_batch(gaussian_features)
-    colors, depths, alphas, feats, contribs = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+    colors, depths, alphas, feats, contribs, picks = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
     groups = {}
     for i in range(n):
         groups.setdefault(int(view_to_batch[i]), []).append(i)
@@ -492,7 +520,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[idx[0]], projmatrix=full[idx[0]], sh_degree=degree, campos=campos[idx[0]],
             prefiltered=False, list_capacity=list_capacity * len(idx), sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks)
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         out = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
                               take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
@@ -501,13 +529,16 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         col, dep = out[0], out[2]
         if len(idx) == n and contiguous:  # every view in this one launch set: hand its outputs on as they are
             return _fused_result(col, dep if depth_mode is not None else None, out[3] if return_alpha else None,
-                                 return_alpha, out[fi] if has_feat else None, out[-1] if want_contrib else None)
+                                 return_alpha, out[fi] if has_feat else None, out[ci] if want_contrib else None,
+                                 out[-1] if want_picks else None)
         for k, i in enumerate(idx):
             colors[i], depths[i] = col[k], dep[k]
             if has_feat:
                 feats[i] = out[fi][k]
             if want_contrib:
-                contribs[i] = Contributions(*(t[k] for t in out[-1]))
+                contribs[i] = Contributions(*(t[k] for t in out[ci]))
+            if want_picks:
+                picks[i] = PixelPicks(*(t[k] for t in out[-1]))
             if return_alpha:
                 alphas[i] = out[3][k]
     for i in single:
@@ -526,7 +557,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             input_scale=None if scale is None else scale[i:i + 1], sh_channel_major=True, aux_affine=aux_affine,
             tanfov=None if tanfov is None else tanfov[i], sh_max_degree=sh_cap,
             scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks)
         means = g_means[b]
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
@@ -537,7 +568,9 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         if has_feat:
             feats[i] = out[fi]
         if want_contrib:
-            contribs[i] = out[-1]
+            contribs[i] = out[ci]
+        if want_picks:
+            picks[i] = out[-1]
         if return_alpha:
             alphas[i] = out[3]
     # one view (GGRt's usual call): a view of the rasterizer's output instead of a stack — no copy kernel forward,
@@ -545,16 +578,18 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     stack = lambda ts: ts[0].unsqueeze(0) if len(ts) == 1 else torch.stack(ts)
     return _fused_result(stack(colors), stack(depths) if depth_mode is not None else None,
                          stack(alphas) if return_alpha else None, return_alpha, stack(feats) if has_feat else None,
-                         _stack_contributions(contribs) if want_contrib else None)
+                         _stack_contributions(contribs) if want_contrib else None, _stack_picks(picks) if want_picks else None)
 
 
-def _fused_result(color, depth, alpha, return_alpha, features=None, contributions=None):
+def _fused_result(color, depth, alpha, return_alpha, features=None, contributions=None, picks=None):
     """render_views_fused's result: (color, depth) as always, (color, depth, alpha) with return_alpha; the rendered feature
-    channels, when asked for, come behind them, and the contributions, when asked for, last"""
+    channels, when asked for, come behind them, the contributions, when asked for, behind those, and the picks last"""
     res = (color, depth, alpha) if return_alpha else (color, depth)
     if features is not None:
         res += (features,)
-    return res if contributions is None else res + (contributions,)
+    if contributions is not None:
+        res += (contributions,)
+    return res if picks is None else res + (picks,)
 
 
 def contribution_keep_mask(contributions: Contributions, min_weight_max: Optional[float] = None,
@@ -620,21 +655,25 @@ class DecoderSplattingCUDA(nn.Module):
     def forward(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                 image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None,
                 return_alpha: bool = False, gaussian_features: Optional[Tensor] = None,
-                return_contributions: bool = False) -> DecoderOutput:
+                *, return_picks: bool = False, return_contributions: bool = False) -> DecoderOutput:
         """``scissor=(x0, y0, x1, y1)`` (extension, fused path): render only that pixel window's tiles — the
         deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``.  ``return_alpha=True`` (extension): the output's
         ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it.
         ``gaussian_features`` [b,g,K] (extension, 1 <= K <= 32): the output's ``features`` [b,v,K,h,w] holds those per-Gaussian
         channels composited through the colour pass's own launch set (Σ f·α·T, no background), differentiable.
         ``return_contributions=True`` (extension): the output's ``contributions`` holds [b,v,g] tensors — per view and
-        Gaussian Σ w, max w and the pixel count of the colour pass (``contribution_keep_mask`` turns them into a pruning mask)."""
+        Gaussian Σ w, max w and the pixel count of the colour pass (``contribution_keep_mask`` turns them into a pruning mask).
+        ``return_picks=True`` (extension; keyword-only): the output's ``picks`` holds [b,v,h,w] planes — per pixel the median depth
+        and its Gaussian, the dominant blend weight and its Gaussian (indices within the batch element's g Gaussians, −1 where
+        nothing was composited) and the contributor count of the colour pass; not differentiable (``pick_values``)."""
         b, v = extrinsics.shape[:2]
         alpha = None
         has_feat = gaussian_features is not None
-        want_contrib = bool(return_contributions)
-        fi = -2 if want_contrib else -1
+        want_contrib, want_picks = bool(return_contributions), bool(return_picks)
+        fi, ci = _tail_index(want_contrib, want_picks)
         unflat = lambda t: t.reshape(b, v, *t.shape[1:])
-        unflat_c = lambda c: Contributions(*(unflat(t) for t in c)) if want_contrib else None
+        unflat_c = lambda out: Contributions(*(unflat(t) for t in out[ci])) if want_contrib else None
+        unflat_p = lambda out: PixelPicks(*(unflat(t) for t in out[-1])) if want_picks else None
         if scissor is not None and not (self.fused_inputs and self.fused_depth):
             raise ValueError("scissor needs the fused call site (fused_inputs and fused_depth)")
         bg = self.background_color.to(far.device)[None].expand(b * v, 3)
@@ -644,13 +683,13 @@ class DecoderSplattingCUDA(nn.Module):
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
                 scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
-                gaussian_features=gaussian_features, return_contributions=want_contrib)
+                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks)
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]),
                                  None if depth is None else depth.reshape(b, v, *depth.shape[1:]), alpha,
-                                 unflat(out[fi]) if has_feat else None, unflat_c(out[-1]))
+                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out))
         if depth_mode is not None and self.fused_depth:
             out = render_color_and_depth(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
@@ -658,22 +697,24 @@ class DecoderSplattingCUDA(nn.Module):
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
                 sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
                 gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                **self._ellipsoids(gaussians, v))
+                return_picks=want_picks, **self._ellipsoids(gaussians, v))
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]), alpha,
-                                 unflat(out[fi]) if has_feat else None, unflat_c(out[-1]))
+                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out))
         color = render_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                             image_shape, bg, self._per_view(gaussians.means, v),
                             self._opt_per_view(gaussians.covariances, v), self._per_view(gaussians.harmonics, v),
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
                             antialiasing=self.antialiasing, return_alpha=return_alpha,
                             gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                            **self._ellipsoids(gaussians, v))
-        features, contributions = None, None
-        if want_contrib:   # (the last element; what is left is the result without it)
-            color, contributions = (color[:-1] if len(color) > 2 else color[0]), unflat_c(color[-1])
+                            return_picks=want_picks, **self._ellipsoids(gaussians, v))
+        features, contributions, picks = None, None, None
+        if want_picks:   # (the last element; what is left is the result without it)
+            color, picks = (color[:-1] if len(color) > 2 else color[0]), PixelPicks(*(unflat(t) for t in color[-1]))
+        if want_contrib:   # (then the contributions)
+            color, contributions = (color[:-1] if len(color) > 2 else color[0]), Contributions(*(unflat(t) for t in color[-1]))
         if has_feat:
             color, features = color[:-1] if return_alpha else color[0], unflat(color[-1])
         if return_alpha:   # (the colour pass's; the reference's separate depth pass below has its own)
@@ -682,7 +723,7 @@ class DecoderSplattingCUDA(nn.Module):
         color = color.reshape(b, v, *color.shape[1:])
         depth = None if depth_mode is None else self.render_depth(gaussians, extrinsics, intrinsics, near, far,
                                                                   image_shape, depth_mode)
-        return DecoderOutput(color, depth, alpha, features, contributions)
+        return DecoderOutput(color, depth, alpha, features, contributions, picks)
 
     def render_depth(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                      image_shape, mode: DepthRenderingMode = "depth") -> Tensor:

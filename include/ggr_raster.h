@@ -487,6 +487,50 @@ typedef struct GgrContributionPass {
 int ggr_contributions(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrContributionPass* pass,
                       void* stream);
 
+/* ---- the pick pass: per-PIXEL picks over a forward's lists (ABI 11, additive) ---------------------------------------------------
+ * Which Gaussian a pixel shows.  For a pixel, walk its tile's list in order with the colour blend's rules.  An entry is LIVE at
+ * the pixel exactly as in the contribution pass above: power <= 0, α >= 1/255 after the 0.99 cap (the compensated opacity's α
+ * under antialiasing), and in front of the entry that would take T below 1e-4.  T_before is the colour blend's T at that
+ * entry and w = α·T_before the colour's own weight, bit for bit.  Five planes, [H,W] ([V,H,W] for a launch set):
+ *     out_median_index int32    the id of the LAST live entry with T_before > 0.5 — 2DGS / gsplat's median rule; the first live
+ *                               entry always qualifies                                             (no live entry: −1)
+ *     out_median_depth float32  that Gaussian's DEPTH VALUE                                         (no live entry: 0)
+ *     out_max_index    int32    the id of the live entry with the largest w; among equal w the earliest in the list
+ *                               (strict > while walking)                                           (no live entry: −1)
+ *     out_max_weight   float32  that w                                                             (no live entry: 0)
+ *     out_count        int32    the number of live entries                                         (no live entry: 0)
+ * The depth value is what out_depth blends: view z, aux_precomp, or max(a + b·z/s, 0) under aux_affine.  Ids are Gaussian
+ * indices in [0,P) WITHIN THE VIEW'S GAUSSIAN SET (the list id, a row of the [V·P] arrays, minus view·P).  Pixels of tiles
+ * outside the scissor window, and of frames with num_rendered == 0, get the "no live entry" values.  The call writes EVERY
+ * element of every requested plane: the caller clears nothing.  Forward only: the planes are not differentiable (a host gathers
+ * a differentiable per-Gaussian value at out_median_index for a gradient through the median depth).  All five planes are
+ * order-independent — no sum, no atomic — hence bit-identical from run to run and across the forms of the depth sort.
+ * Relation to the other planes: count == 0 ⇔ alpha == 0; max_weight <= alpha; Σ_pixels count == Σ_Gaussians out_pixel_count of
+ * the contribution pass, and the largest max_weight is the largest out_weight_max.
+ *
+ * Protocol, limits and validation, as ggr_contributions: ggr_pixel_picks runs AFTER ggr_forward* (any variant, any mode) on the
+ * same stream, over that forward's geom_buffer, image_buffer, binning_buffer (as the forward RETURNED it) and num_rendered; a
+ * no_backward forward's smaller buffers serve as well.  `views` NULL: one view; else the GgrViews of the launch set — only
+ * num_views / num_sets are read.  It allocates nothing, reads nothing back and is hipGraph-capturable.  Each output may be NULL
+ * (not computed), at least one must not be.  GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the
+ * struct, a nonzero `reserved`, all five outputs NULL, or a NULL buffer the call needs. */
+typedef struct GgrPickPass {
+    int32_t struct_size;            /* sizeof(GgrPickPass) */
+    int32_t reserved;               /* 0 */
+    const void* geom_buffer;        /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;     /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;           /* the forward's (−1: sync-free mode) */
+    int32_t* out_median_index;      /* device [H,W] / [V,H,W] or NULL */
+    float* out_median_depth;        /* device [H,W] / [V,H,W] or NULL */
+    int32_t* out_max_index;         /* device [H,W] / [V,H,W] or NULL */
+    float* out_max_weight;          /* device [H,W] / [V,H,W] or NULL */
+    int32_t* out_count;             /* device [H,W] / [V,H,W] or NULL */
+} GgrPickPass;
+
+int ggr_pixel_picks(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrPickPass* pass,
+                    void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
