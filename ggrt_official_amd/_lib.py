@@ -136,6 +136,18 @@ def pick_pass(**fields) -> GgrPickPass:
     return GgrPickPass(struct_size=C.sizeof(GgrPickPass), **fields)
 
 
+class GgrDistortionPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
+                ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
+                ("out_distortion", C.c_void_p), ("totals", C.c_void_p), ("dL_dout_distortion", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_zeroed", C.c_int32), ("reserved2", C.c_int32)]
+
+
+def distortion_pass(**fields) -> GgrDistortionPass:
+    """The argument of ggr_distortion_forward / ggr_distortion_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrDistortionPass(struct_size=C.sizeof(GgrDistortionPass), **fields)
+
+
 FWD_STAGES = ["preprocess", "depth_sort", "tile_count", "tile_scatter", "blend", "colour_side_stream", "tile_sort"]
 DEPTH_SORT = {"auto": 0, "global": 1, "per_tile": 2, "global_3pass": 0x101}
 DEPTH_SORT_NO_BUCKETS = 0x100      # IN flag: never the global sort's bucket form (include/ggr_raster.h)
@@ -188,6 +200,8 @@ SYMBOLS = [
     ("ggr_features_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrFeaturePass), C.c_void_p]),
     ("ggr_contributions", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrContributionPass), C.c_void_p]),
     ("ggr_pixel_picks", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrPickPass), C.c_void_p]),
+    ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
+    ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),

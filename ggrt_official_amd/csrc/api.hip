@@ -9,6 +9,7 @@
 #include "blend_feat.h"
 #include "blend_contrib.h"
 #include "blend_pick.h"
+#include "blend_dist.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1143,6 +1144,79 @@ int ggr_pixel_picks(const GgrSettings* st, const GgrViews* views, const GgrPickP
     ggr::launch_blend_pick(W, H, im.ranges, (const uint32_t*)pp->binning_buffer, g.splat, pp->out_median_index,
                            pp->out_median_depth, pp->out_max_index, pp->out_max_weight, pp->out_count, V, P1, scissored ? 1 : 0, s);
     KCHECK(st->debug != 0, s, "blend_pick");
+    return GGR_OK;
+}
+
+// ---- the distortion pass (blend_dist.hip): the depth-distortion plane over a forward's lists, and its backward -----------------
+namespace {
+int distortion_pass_check(const GgrSettings* st, const GgrViews* views, const GgrDistortionPass* dp, bool backward, int* V) {
+    if (!st || !dp) return fail(GGR_E_INVALID, "null settings / distortion pass");
+    if (dp->struct_size < (int32_t)sizeof(GgrDistortionPass))
+        return fail(GGR_E_INVALID, "GgrDistortionPass.struct_size %d is smaller than the %d bytes of its fields", (int)dp->struct_size,
+                    (int)sizeof(GgrDistortionPass));
+    if (dp->reserved != 0 || dp->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrDistortionPass.reserved must be 0, not %d / %d", (int)dp->reserved, (int)dp->reserved2);
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (!dp->out_distortion) return fail(GGR_E_INVALID, "GgrDistortionPass.out_distortion is NULL");
+    if (!dp->geom_buffer || !dp->image_buffer) return fail(GGR_E_INVALID, "GgrDistortionPass: null geom / image buffer of the forward");
+    if (dp->num_rendered != 0 && !dp->binning_buffer) return fail(GGR_E_INVALID, "GgrDistortionPass.binning_buffer is NULL");
+    if (backward) {
+        if (!dp->totals) return fail(GGR_E_INVALID, "GgrDistortionPass.totals is NULL");
+        if (!dp->dL_dout_distortion) return fail(GGR_E_INVALID, "GgrDistortionPass.dL_dout_distortion is NULL");
+        if (!dp->scratch) return fail(GGR_E_INVALID, "GgrDistortionPass.scratch is NULL");
+    }
+    *V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        *V = views->num_views;
+    }
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_distortion_forward(const GgrSettings* st, const GgrViews* views, const GgrDistortionPass* dp, void* stream) {
+    g_err[0] = 0;
+    int V = 1;
+    const int rc = distortion_pass_check(st, views, dp, false, &V);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height;
+    const size_t pixels = (size_t)V * (size_t)W * (size_t)H;
+    if (pixels == 0) return GGR_OK;
+    if (P1 == 0 || dp->num_rendered == 0) {   // no list entry anywhere: the plane and the totals are zero
+        HIP_TRY(hipMemsetAsync(dp->out_distortion, 0, pixels * sizeof(float), s));
+        if (dp->totals) HIP_TRY(hipMemsetAsync(dp->totals, 0, 2 * pixels * sizeof(float), s));
+        return GGR_OK;
+    }
+    GeomLayout g = ggr_carve_geom((void*)dp->geom_buffer, (size_t)P1 * V, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)dp->image_buffer, W, H, V);
+    const bool scissored = (st->scissor[0] | st->scissor[1] | st->scissor[2] | st->scissor[3]) != 0;
+    ggr::launch_blend_dist_fwd(W, H, im.ranges, (const uint32_t*)dp->binning_buffer, g.splat, dp->out_distortion, dp->totals, V,
+                               scissored ? 1 : 0, s);
+    KCHECK(st->debug != 0, s, "blend_dist_fwd");
+    return GGR_OK;
+}
+
+int ggr_distortion_backward(const GgrSettings* st, const GgrViews* views, const GgrDistortionPass* dp, void* stream) {
+    g_err[0] = 0;
+    int V = 1;
+    const int rc = distortion_pass_check(st, views, dp, true, &V);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height;
+    BwdScratch sc = ggr_carve_bwd(dp->scratch, (size_t)P1, (size_t)V);
+    if (!dp->scratch_zeroed) HIP_TRY(hipMemsetAsync(dp->scratch, 0, sc.bytes, s));
+    if (P1 == 0 || dp->num_rendered == 0 || (size_t)W * H == 0) return GGR_OK;
+    GeomLayout g = ggr_carve_geom((void*)dp->geom_buffer, (size_t)P1 * V, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)dp->image_buffer, W, H, V);
+    ggr::launch_blend_dist_bwd(W, H, im.ranges, (const uint32_t*)dp->binning_buffer, g.splat, dp->out_distortion, dp->totals,
+                               dp->dL_dout_distortion, sc.grad2d, V, s);
+    KCHECK(st->debug != 0, s, "blend_dist_bwd");
     return GGR_OK;
 }
 

@@ -19,6 +19,7 @@
 // carries the feature loss on unchanged.  Per entry a wave has KC + 6 sums over its 64 pixels; RB entries at a time go through
 // ONE transposing butterfly (each level halves the values a lane holds: ≈ one exchange + one add per value instead of six),
 // after which every lane owns (KC + 8)/8 — or /16 — finished sums of one entry and commits them with one atomic each.
+#include "blend_butterfly.h"
 #include "blend_common.h"
 #include "blend_feat.h"
 
@@ -161,37 +162,8 @@ void launch_blend_feat_fwd(int W, int H, const uint2* ranges, const uint32_t* po
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float feat_dpp(float v) {   // (every lane has a source under the controls used below)
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
-// One level of the transposing butterfly over v[0 .. 2·HALF): the lanes whose bit is clear keep the lower half of the values,
-// their partners the upper half, each adds what the partner sends.  Afterwards v[0 .. HALF) is live.
-template <int HALF, int CTRL>
-__device__ __forceinline__ void fold_dpp(float* v, bool upper) {
-#pragma unroll
-    for (int i = 0; i < HALF; i++) {
-        const float keep = upper ? v[i + HALF] : v[i], send = upper ? v[i] : v[i + HALF];
-        v[i] = keep + feat_dpp<CTRL>(send);
-    }
-}
-template <int HALF>
-__device__ __forceinline__ void fold_swap32(float* v) {   // lanes 0-31 keep the lower half, lanes 32-63 the upper
-#pragma unroll
-    for (int i = 0; i < HALF; i++) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + HALF]), false, false);
-        v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-}
-template <int HALF>
-__device__ __forceinline__ void fold_swap16(float* v) {   // even 16-lane rows keep the lower half, odd rows the upper
-#pragma unroll
-    for (int i = 0; i < HALF; i++) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + HALF]), false, false);
-        v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-}
+// (feat_dpp, fold_dpp, fold_swap32, fold_swap16 — the transposing butterfly's levels — live in blend_butterfly.h: the distortion
+//  pass, blend_dist.hip, reduces its sums the same way)
 
 // KC channels per walk of the list, RB entries per butterfly.  A lane's values of one entry: KC × w·dF_k, then the six
 // geometric terms in record order (mean x, y; conic xx, xy, yy; opacity) and two zeros: VC = KC + 8 values, RB·VC in all.

@@ -103,11 +103,19 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
     blend composited there, the Gaussian at which the transmittance crosses 1/2 and its depth value, the Gaussian of the
     largest blend weight and that weight, and the number of composited entries (include/ggr_raster.h GgrPickPass).  Not
     differentiable — ``pick_values`` gathers a differentiable per-Gaussian value at an index plane.  False: nothing extra
-    allocated or called."""
+    allocated or called.
+
+    ``return_distortion`` (bool, default False; keyword only), kept beside the tuple in the same way: also return, behind alpha
+    and features and in front of the contributions and picks, ``distortion`` [H,W] ([V,H,W] from ``rasterize_views``): per
+    pixel the depth-distortion regulariser of Mip-NeRF 360 / 2DGS over the entries the colour blend composited there,
+    2·Σ_{j<i} w_i·w_j·(d_i − d_j) with w = α·T and d the depth value the depth plane blends (include/ggr_raster.h
+    GgrDistortionPass; = Σ_ij w_i·w_j·|d_i − d_j| for view z and for ``aux_affine`` with b >= 0).  Differentiable: its gradient
+    flows to every input the depth plane's does.  False: nothing extra allocated or called."""
     return_contributions = False   # (instances made by `_make` from the bare items)
     return_picks = False
+    return_distortion = False
 
-    def __new__(cls, *args, return_contributions=False, return_picks=False, **kw):
+    def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, **kw):
         n = len(_RasterizationSettingsFields._fields)
         if len(args) == n + 2:
             args, return_contributions, return_picks = args[:n], args[n], args[n + 1]
@@ -116,22 +124,26 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         self = super().__new__(cls, *args, **kw)
         self.return_contributions = bool(return_contributions)
         self.return_picks = bool(return_picks)
+        self.return_distortion = bool(return_distortion)
         return self
 
     def _replace(self, **kw):
         on = kw.pop("return_contributions", self.return_contributions)
         picks = kw.pop("return_picks", self.return_picks)
+        dist = kw.pop("return_distortion", self.return_distortion)
         new = super()._replace(**kw)
         new.return_contributions = bool(on)
         new.return_picks = bool(picks)
+        new.return_distortion = bool(dist)
         return new
 
     def _asdict(self):
-        return dict(super()._asdict(), return_contributions=self.return_contributions, return_picks=self.return_picks)
+        return dict(super()._asdict(), return_distortion=self.return_distortion, return_contributions=self.return_contributions,
+                    return_picks=self.return_picks)
 
     def __repr__(self):
-        return (super().__repr__()[:-1] + f", return_contributions={self.return_contributions!r}"
-                f", return_picks={self.return_picks!r})")
+        return (super().__repr__()[:-1] + f", return_distortion={self.return_distortion!r}"
+                f", return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
 
 
 class Contributions(NamedTuple):
@@ -283,6 +295,30 @@ def _pixel_picks(lib, st, vw, geom, img, binb, num_rendered, shape, dev, stream)
                         out_max_index=xi.data_ptr(), out_max_weight=xw.data_ptr(), out_count=cnt.data_ptr())
     _check(lib.ggr_pixel_picks(C.byref(st), _byref(vw), C.byref(pp), stream), "ggr_pixel_picks")
     return md, mi, xw, xi, cnt
+
+
+def _distortion_pass(geom, img, binb, num_rendered, plane, totals, **more):
+    return _lib.distortion_pass(reserved=0, geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
+                                num_rendered=int(num_rendered), out_distortion=plane.data_ptr(), totals=_ptr(totals), **more)
+
+
+def _distortion_forward(lib, st, vw, geom, img, binb, num_rendered, shape, with_totals, dev, stream):
+    """ggr_distortion_forward over the buffers of the forward that has just returned: the plane of `shape` ([H,W] / [V,H,W]) and,
+    when a backward may follow, the per-pixel totals it needs ([2,H,W] / [V,2,H,W]).  The call writes every element."""
+    plane = torch.empty(shape, dtype=torch.float32, device=dev)
+    totals = torch.empty(shape[:-2] + (2,) + shape[-2:], dtype=torch.float32, device=dev) if with_totals else None
+    dp = _distortion_pass(geom, img, binb, num_rendered, plane, totals)
+    _check(lib.ggr_distortion_forward(C.byref(st), _byref(vw), C.byref(dp), stream), "ggr_distortion_forward")
+    return plane, totals
+
+
+def _distortion_backward(lib, st, vw, geom, img, binb, num_rendered, plane, totals, grad_out, scratch, zeroed, stream):
+    """ggr_distortion_backward: the distortion loss's terms — the 2D mean, conic, opacity and the depth value — go into `scratch`
+    ahead of ggr_backward*, which is then told that the scratch is in use (scratch_zeroed = 1) and given a depth gradient (zeros
+    if the loss has none), so that it carries the depth-value term on."""
+    dp = _distortion_pass(geom, img, binb, num_rendered, plane, totals, dL_dout_distortion=grad_out.data_ptr(),
+                          scratch=scratch.data_ptr(), scratch_zeroed=int(zeroed))
+    _check(lib.ggr_distortion_backward(C.byref(st), _byref(vw), C.byref(dp), stream), "ggr_distortion_backward")
 
 
 def _with_contributions(out, on: bool, picks: bool = False):
@@ -651,6 +687,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             if feat_c is not None:   # K feature channels over the lists this forward has just built (csrc/blend_feat.hip)
                 feat_out = torch.empty((feat_c.shape[1], H, W), dtype=torch.float32, device=dev)
                 _features_forward(lib, st, None, feat_c, geom, img, holder.get("bin"), fout.num_rendered, feat_out, stream)
+            dist_out = dist_tot = None
+            if bool(getattr(rs, "return_distortion", False)):   # the depth-distortion plane over the same lists (csrc/blend_dist.hip)
+                dist_out, dist_tot = _distortion_forward(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, (H, W),
+                                                         not infer, dev, stream)
             want_contrib = bool(getattr(rs, "return_contributions", False))
             contrib = ()
             if want_contrib:   # per-Gaussian statistics of the weights this forward has just blended (csrc/blend_contrib.hip)
@@ -671,13 +711,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                          None if aux is None else aux.shape)
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg, view, proj, cam, radii, geom,
-                              img, holder.get("bin"), aux_c, scratch, feat_c, feat_out)
+                              img, holder.get("bin"), aux_c, scratch, feat_c, feat_out, dist_out, dist_tot)
         ctx.scratch_fresh = scratch is not None  # (a second backward over this forward clears a scratch of its own)
         ctx.mark_non_differentiable(radii)
-        ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape)
+        ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
         out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
         if feat_c is not None:
             out += (feat_out,)
+        if dist_out is not None:
+            out += (dist_out,)
         if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
             ctx.mark_non_differentiable(radii, *contrib, *picks)
             out += contrib + picks
@@ -688,10 +730,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch, feat,
-         feat_out) = ctx.saved_tensors
-        want_alpha, has_feat, feat_shape = ctx.outs
+         feat_out, dist_out, dist_tot) = ctx.saved_tensors
+        want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
-        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' and picks' None)
+        grad_feat = grad_extra[int(want_alpha)] if has_feat else None
+        grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions' and picks' None)
         P, M, H, W = ctx.dims
         dev = means3D.device
         need_pose = any(ctx.needs_input_grad[8:11])
@@ -702,6 +745,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_color = _f32c(grad_color)
             grad_depth = _f32c(grad_depth)
             grad_alpha = _f32c(grad_alpha)   # (None: the default backward kernels)
+            if grad_dist is not None and grad_depth is None:   # ggr_backward carries the depth-value term on with a depth gradient
+                grad_depth = torch.zeros((H, W), dtype=torch.float32, device=dev)
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
             d_means3D = torch.empty((P, 3), dtype=torch.float32, device=dev)
             d_means2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
@@ -727,6 +772,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                 d_feat = torch.empty_like(feat)
                 _features_backward(lib, st, None, feat, geom, img, binb, ctx.num_rendered, feat_out, _f32c(grad_feat), d_feat,
                                    scratch, zeroed, stream)
+                zeroed = True
+            if grad_dist is not None:   # … and the distortion loss's, the depth value's among them
+                _distortion_backward(lib, st, None, geom, img, binb, ctx.num_rendered, dist_out, dist_tot, _f32c(grad_dist),
+                                     scratch, zeroed, stream)
                 zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
@@ -875,6 +924,10 @@ class _RasterizeViews(torch.autograd.Function):
             if feat_c is not None:
                 feat_out = torch.empty((V, feat_c.shape[1], H, W), dtype=torch.float32, device=dev)
                 _features_forward(lib, st, vw, feat_c, geom, img, holder.get("bin"), fout.num_rendered, feat_out, stream)
+            dist_out = dist_tot = None
+            if bool(getattr(rs, "return_distortion", False)):
+                dist_out, dist_tot = _distortion_forward(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, (V, H, W),
+                                                         not infer, dev, stream)
             want_contrib = bool(getattr(rs, "return_contributions", False))
             contrib = ()
             if want_contrib:
@@ -894,13 +947,15 @@ class _RasterizeViews(torch.autograd.Function):
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None,
                    means2D is not None)
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg_c, view, proj, cam, radii, geom,
-                              img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out)
+                              img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out, dist_out, dist_tot)
         ctx.scratch_fresh = scratch is not None
         ctx.mark_non_differentiable(radii)
-        ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape)
+        ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
         out = (color, radii, depth, alpha) if want_alpha else (color, radii, depth)
         if feat_c is not None:
             out += (feat_out,)
+        if dist_out is not None:
+            out += (dist_out,)
         if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
             ctx.mark_non_differentiable(radii, *contrib, *picks)
             out += contrib + picks
@@ -911,10 +966,11 @@ class _RasterizeViews(torch.autograd.Function):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, tf, sc_in,
-         fwd_scratch, feat, feat_out) = ctx.saved_tensors
-        want_alpha, has_feat, feat_shape = ctx.outs
+         fwd_scratch, feat, feat_out, dist_out, dist_tot) = ctx.saved_tensors
+        want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
-        grad_feat = grad_extra[1 if want_alpha else 0] if has_feat else None   # (behind it: the contributions' and picks' None)
+        grad_feat = grad_extra[int(want_alpha)] if has_feat else None
+        grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions' and picks' None)
         P, M, H, W, V, B = ctx.dims
         PT = P * B   # rows of the flat [B·P, …] gradient arrays
         dev = means3D.device
@@ -924,6 +980,8 @@ class _RasterizeViews(torch.autograd.Function):
             if grad_color is None:
                 grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
             grad_color, grad_depth, grad_alpha = _f32c(grad_color), _f32c(grad_depth), _f32c(grad_alpha)
+            if grad_dist is not None and grad_depth is None:   # ggr_backward_views carries the depth-value term on with a depth gradient
+                grad_depth = torch.zeros((V, H, W), dtype=torch.float32, device=dev)
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
             form, cov_full, sh_cm = ctx.form
             e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -949,6 +1007,10 @@ class _RasterizeViews(torch.autograd.Function):
                 d_feat = torch.empty_like(feat)
                 _features_backward(lib, st, vw, feat, geom, img, binb, ctx.num_rendered, feat_out, _f32c(grad_feat), d_feat,
                                    scratch, zeroed, stream)
+                zeroed = True
+            if grad_dist is not None:
+                _distortion_backward(lib, st, vw, geom, img, binb, ctx.num_rendered, dist_out, dist_tot, _f32c(grad_dist),
+                                     scratch, zeroed, stream)
                 zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
@@ -1008,7 +1070,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     differentiable like the colour.  With ``raster_settings.return_contributions`` a ``Contributions`` of ``[V,P]`` tensors
     (Σ w, max w, pixel count per view and Gaussian; not differentiable) follows, and with ``raster_settings.return_picks`` a
     ``PixelPicks`` of ``[V,H,W]`` planes (median depth / index, dominant weight / index, contributor count per pixel; indices
-    within the view's Gaussian set; not differentiable) is the very last output."""
+    within the view's Gaussian set; not differentiable) is the very last output.  With ``raster_settings.return_distortion``
+    the depth-distortion plane ``distortion [V,H,W]`` (differentiable) stands behind alpha and the features, in front of both."""
     shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
     scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
     if (shs is None) == (colors_precomp is None):
@@ -1129,7 +1192,9 @@ class GaussianRasterizer(nn.Module):
         ``features [K,H,W]`` = Σ f·α·T (no background term) as its LAST element, differentiable.  With
         ``return_contributions=True`` in the settings a ``Contributions(weight_sum, weight_max, pixel_count)`` of [P] tensors
         follows behind everything else (not differentiable), and with ``return_picks=True`` a ``PixelPicks(median_depth,
-        median_index, max_weight, max_index, count)`` of [H,W] planes behind that (not differentiable; ``pick_values``)."""
+        median_index, max_weight, max_index, count)`` of [H,W] planes behind that (not differentiable; ``pick_values``).  With
+        ``return_distortion=True`` the depth-distortion plane ``distortion [H,W]`` (differentiable) stands behind alpha and the
+        features, in front of both."""
         shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
         scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):

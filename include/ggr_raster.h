@@ -531,6 +531,54 @@ typedef struct GgrPickPass {
 int ggr_pixel_picks(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrPickPass* pass,
                     void* stream);
 
+/* ---- the distortion pass: the depth-distortion plane over a forward's lists, differentiable (ABI 11, additive) -----------------
+ * The regulariser of Mip-NeRF 360 / 2DGS.  For a pixel, take the entries the colour blend composited there (LIVE exactly as in the
+ * contribution pass above), in list order i = 1..n, with w_i = α_i·T_i the colour's own weight, bit for bit, and d_i the
+ * Gaussian's DEPTH VALUE — what out_depth blends: view z, aux_precomp, or max(a + b·z/s, 0) under aux_affine:
+ *     A_i = Σ_{j<i} w_j      B_i = Σ_{j<i} w_j·d_j
+ *     out_distortion = 2·Σ_i w_i·(d_i·A_i − B_i)           ( = 2·Σ_{j<i} w_i·w_j·(d_i − d_j) )
+ * Whenever d does not decrease along the list this is Σ_{i,j} w_i·w_j·|d_i − d_j|: so for view z (the lists are sorted by it) and
+ * for aux_affine with b >= 0.  For an arbitrary aux_precomp it is the signed, list-ordered form above; a caller who wants
+ * another parametrisation (disparity, normalised distance) passes an aux_precomp that is monotone in view z.  0 where nothing,
+ * or one entry only, was composited; pixels of tiles outside the scissor window and of frames with num_rendered == 0 get 0.
+ * The call writes EVERY element of the plane.  The sum runs per pixel in list order, with every d taken relative to the depth
+ * value of the pixel's first composited entry (the sum does not depend on the origin; its rounding does): bit-identical from run
+ * to run, across the forms of the depth sort and between a training and a no_backward forward.
+ * (The SQUARED variant needs no pass: Σ_{j<i} w_i·w_j·(d_i − d_j)² = alpha·F[d²] − F[d]² with F the feature pass's planes of the
+ * per-Gaussian channels d and d², and alpha the accumulated opacity.)
+ *
+ * Protocol, as the feature pass.  ggr_distortion_forward runs AFTER ggr_forward* (any variant, any mode) on the same stream, over
+ * that forward's geom_buffer, image_buffer, binning_buffer (as the forward RETURNED it) and num_rendered; a no_backward forward's
+ * smaller buffers serve as well.  `totals` ([2,H,W] / [V,2,H,W] floats, or NULL when no backward will follow) receives what the
+ * backward needs beside the plane: per pixel Σ w and the origin-relative Σ w·d.  ggr_distortion_backward runs BEFORE that frame's
+ * ggr_backward*: it adds the distortion loss's gradient w.r.t. the 2D mean, conic, opacity AND depth value into the backward
+ * scratch (clearing it first unless scratch_zeroed = 1), and the caller then passes scratch_zeroed = 1 to ggr_backward*, which
+ * carries the sums on to means3D, covariance / scale / rotation, opacity, the camera and dL_daux.  It may share a scratch with
+ * ggr_features_backward, in either order (the second one called gets scratch_zeroed = 1).  ggr_backward* carries the depth-value
+ * term on only when it is given a dL_dout_depth plane: a caller without a loss on out_depth passes a plane of zeros (and, with
+ * aux_precomp, a dL_daux output).  `views` NULL: one view; else the GgrViews of the launch set — only num_views / num_sets are
+ * read.  Both calls allocate nothing, read nothing back and are hipGraph-capturable.  GGR_E_INVALID, before anything is
+ * enqueued, for a struct_size smaller than the struct, a nonzero `reserved`, or a NULL buffer / plane the call needs. */
+typedef struct GgrDistortionPass {
+    int32_t struct_size;               /* sizeof(GgrDistortionPass) */
+    int32_t reserved;                  /* 0 */
+    const void* geom_buffer;           /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;        /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;              /* the forward's (−1: sync-free mode) */
+    float* out_distortion;             /* device [H,W] / [V,H,W].  forward: OUT.  backward: IN — what the forward wrote */
+    float* totals;                     /* device [2,H,W] / [V,2,H,W].  forward: OUT, or NULL.  backward: IN — what the forward wrote */
+    const float* dL_dout_distortion;   /* backward: device, shape of out_distortion */
+    void* scratch;                     /* backward: the ggr_backward_scratch_bytes(_views) buffer this frame's ggr_backward* gets */
+    int32_t scratch_zeroed;            /* backward: 1 = `scratch` is already clear (GgrBackwardIn.scratch_zeroed's meaning) */
+    int32_t reserved2;                 /* 0 */
+} GgrDistortionPass;
+
+int ggr_distortion_forward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrDistortionPass* pass,
+                           void* stream);
+int ggr_distortion_backward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrDistortionPass* pass,
+                            void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
