@@ -148,6 +148,19 @@ def distortion_pass(**fields) -> GgrDistortionPass:
     return GgrDistortionPass(struct_size=C.sizeof(GgrDistortionPass), **fields)
 
 
+class GgrAbsgradPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
+                ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
+                ("out_color", C.c_void_p), ("out_depth", C.c_void_p), ("dL_dout_color", C.c_void_p),
+                ("dL_dout_depth", C.c_void_p), ("dL_dout_alpha", C.c_void_p), ("out_absgrad", C.c_void_p),
+                ("out_grad", C.c_void_p)]
+
+
+def absgrad_pass(**fields) -> GgrAbsgradPass:
+    """The argument of ggr_means2d_absgrad (include/ggr_raster.h), struct_size filled in."""
+    return GgrAbsgradPass(struct_size=C.sizeof(GgrAbsgradPass), **fields)
+
+
 FWD_STAGES = ["preprocess", "depth_sort", "tile_count", "tile_scatter", "blend", "colour_side_stream", "tile_sort"]
 DEPTH_SORT = {"auto": 0, "global": 1, "per_tile": 2, "global_3pass": 0x101}
 DEPTH_SORT_NO_BUCKETS = 0x100      # IN flag: never the global sort's bucket form (include/ggr_raster.h)
@@ -202,6 +215,7 @@ SYMBOLS = [
     ("ggr_pixel_picks", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrPickPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
+    ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),

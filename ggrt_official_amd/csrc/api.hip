@@ -10,6 +10,7 @@
 #include "blend_contrib.h"
 #include "blend_pick.h"
 #include "blend_dist.h"
+#include "blend_absgrad.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1217,6 +1218,48 @@ int ggr_distortion_backward(const GgrSettings* st, const GgrViews* views, const 
     ggr::launch_blend_dist_bwd(W, H, im.ranges, (const uint32_t*)dp->binning_buffer, g.splat, dp->out_distortion, dp->totals,
                                dp->dL_dout_distortion, sc.grad2d, V, s);
     KCHECK(st->debug != 0, s, "blend_dist_bwd");
+    return GGR_OK;
+}
+
+// ---- the absgrad pass (blend_absgrad.hip): per-Gaussian absolute screen-space positional gradients over a forward's lists ------
+int ggr_means2d_absgrad(const GgrSettings* st, const GgrViews* views, const GgrAbsgradPass* ap, void* stream) {
+    g_err[0] = 0;
+    if (!st || !ap) return fail(GGR_E_INVALID, "null settings / absgrad pass");
+    if (ap->struct_size < (int32_t)sizeof(GgrAbsgradPass))
+        return fail(GGR_E_INVALID, "GgrAbsgradPass.struct_size %d is smaller than the %d bytes of its fields", (int)ap->struct_size,
+                    (int)sizeof(GgrAbsgradPass));
+    if (ap->reserved != 0) return fail(GGR_E_INVALID, "GgrAbsgradPass.reserved must be 0, not %d", (int)ap->reserved);
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    const bool no_pixels = (size_t)st->image_width * (size_t)st->image_height == 0;   // (an empty frame has no planes)
+    if (st->num_points > 0 && !ap->out_absgrad) return fail(GGR_E_INVALID, "GgrAbsgradPass.out_absgrad is NULL");
+    if (!ap->geom_buffer || !ap->image_buffer) return fail(GGR_E_INVALID, "GgrAbsgradPass: null geom / image buffer of the forward");
+    if (ap->num_rendered != 0 && !ap->binning_buffer) return fail(GGR_E_INVALID, "GgrAbsgradPass.binning_buffer is NULL");
+    if (!no_pixels && !ap->out_color) return fail(GGR_E_INVALID, "GgrAbsgradPass.out_color is NULL");
+    if (!no_pixels && !ap->dL_dout_color) return fail(GGR_E_INVALID, "GgrAbsgradPass.dL_dout_color is NULL");
+    if (!no_pixels && ap->dL_dout_depth && !ap->out_depth) return fail(GGR_E_INVALID, "GgrAbsgradPass.out_depth is NULL but dL_dout_depth is given");
+    int V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        V = views->num_views;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height;
+    const size_t rows = (size_t)V * (size_t)P1;
+    if (rows == 0) return GGR_OK;
+    HIP_TRY(hipMemsetAsync(ap->out_absgrad, 0, rows * 2 * sizeof(float), s));
+    if (ap->out_grad) HIP_TRY(hipMemsetAsync(ap->out_grad, 0, rows * 2 * sizeof(float), s));
+    if (ap->num_rendered == 0 || (size_t)W * H == 0) return GGR_OK;   // no list entry anywhere
+    GeomLayout g = ggr_carve_geom((void*)ap->geom_buffer, rows, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)ap->image_buffer, W, H, V);
+    ggr::launch_blend_absgrad(W, H, im.ranges, (const uint32_t*)ap->binning_buffer, g.splat, g.colour, im.final_T, ap->out_color,
+                              ap->out_depth, ap->dL_dout_color, ap->dL_dout_depth, ap->dL_dout_alpha, ap->out_absgrad,
+                              ap->out_grad, V, s);
+    KCHECK(st->debug != 0, s, "blend_absgrad");
     return GGR_OK;
 }
 

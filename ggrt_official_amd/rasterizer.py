@@ -110,12 +110,20 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
     pixel the depth-distortion regulariser of Mip-NeRF 360 / 2DGS over the entries the colour blend composited there,
     2·Σ_{j<i} w_i·w_j·(d_i − d_j) with w = α·T and d the depth value the depth plane blends (include/ggr_raster.h
     GgrDistortionPass; = Σ_ij w_i·w_j·|d_i − d_j| for view z and for ``aux_affine`` with b >= 0).  Differentiable: its gradient
-    flows to every input the depth plane's does.  False: nothing extra allocated or called."""
+    flows to every input the depth plane's does.  False: nothing extra allocated or called.
+
+    ``absgrad`` (bool, default False; keyword only), kept beside the tuple in the same way: every backward also runs the absgrad
+    pass (include/ggr_raster.h GgrAbsgradPass) with the gradients it was handed and sets, on the very ``means2D`` tensor the
+    caller passed, ``means2D.absgrad`` = Σ_pixels |∂L_pixel/∂mean2D| ([P,2]; [V,P,2] from ``rasterize_views``; float32, detached,
+    overwritten by each backward) — gsplat's convention, what densification thresholds — and ``means2D.absgrad_signed``, the signed
+    sums of the same terms (= ``means2D.grad[:, :2]`` of a colour / depth / alpha loss).  The terms of a feature or distortion
+    loss are not included.  False: nothing extra allocated, saved or called."""
     return_contributions = False   # (instances made by `_make` from the bare items)
     return_picks = False
     return_distortion = False
+    absgrad = False
 
-    def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, **kw):
+    def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, absgrad=False, **kw):
         n = len(_RasterizationSettingsFields._fields)
         if len(args) == n + 2:
             args, return_contributions, return_picks = args[:n], args[n], args[n + 1]
@@ -125,24 +133,27 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         self.return_contributions = bool(return_contributions)
         self.return_picks = bool(return_picks)
         self.return_distortion = bool(return_distortion)
+        self.absgrad = bool(absgrad)
         return self
 
     def _replace(self, **kw):
         on = kw.pop("return_contributions", self.return_contributions)
         picks = kw.pop("return_picks", self.return_picks)
         dist = kw.pop("return_distortion", self.return_distortion)
+        absg = kw.pop("absgrad", self.absgrad)
         new = super()._replace(**kw)
         new.return_contributions = bool(on)
         new.return_picks = bool(picks)
         new.return_distortion = bool(dist)
+        new.absgrad = bool(absg)
         return new
 
     def _asdict(self):
-        return dict(super()._asdict(), return_distortion=self.return_distortion, return_contributions=self.return_contributions,
+        return dict(super()._asdict(), absgrad=self.absgrad, return_distortion=self.return_distortion, return_contributions=self.return_contributions,
                     return_picks=self.return_picks)
 
     def __repr__(self):
-        return (super().__repr__()[:-1] + f", return_distortion={self.return_distortion!r}"
+        return (super().__repr__()[:-1] + f", absgrad={self.absgrad!r}, return_distortion={self.return_distortion!r}"
                 f", return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
 
 
@@ -319,6 +330,23 @@ def _distortion_backward(lib, st, vw, geom, img, binb, num_rendered, plane, tota
     dp = _distortion_pass(geom, img, binb, num_rendered, plane, totals, dL_dout_distortion=grad_out.data_ptr(),
                           scratch=scratch.data_ptr(), scratch_zeroed=int(zeroed))
     _check(lib.ggr_distortion_backward(C.byref(st), _byref(vw), C.byref(dp), stream), "ggr_distortion_backward")
+
+
+def _means2d_absgrad(lib, st, vw, geom, img, binb, num_rendered, color, depth, grad_color, grad_depth, grad_alpha, shape, sink,
+                     stream):
+    """ggr_means2d_absgrad over the buffers and planes of the forward this backward belongs to, with the gradients the backward
+    was handed: sets `sink.absgrad` and `sink.absgrad_signed` (`shape` + [2], float32, no graph).  The call writes every element."""
+    dev = color.device
+    absg = torch.empty(shape + (2,), dtype=torch.float32, device=dev)
+    signed = torch.empty(shape + (2,), dtype=torch.float32, device=dev)
+    ap = _lib.absgrad_pass(reserved=0, geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
+                           num_rendered=int(num_rendered), out_color=color.data_ptr(),
+                           out_depth=None if grad_depth is None else depth.data_ptr(), dL_dout_color=grad_color.data_ptr(),
+                           dL_dout_depth=_ptr(grad_depth), dL_dout_alpha=_ptr(grad_alpha), out_absgrad=absg.data_ptr(),
+                           out_grad=signed.data_ptr())
+    _check(lib.ggr_means2d_absgrad(C.byref(st), _byref(vw), C.byref(ap), stream), "ggr_means2d_absgrad")
+    sink.absgrad = absg
+    sink.absgrad_signed = signed
 
 
 def _with_contributions(out, on: bool, picks: bool = False):
@@ -710,8 +738,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.in_shapes = (means3D.shape, None if sh is None else sh.shape, opacities.shape,
                          None if aux is None else aux.shape)
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
+        # absgrad: the backward takes the per-pixel totals from the colour and depth planes, and writes to the caller's means2D
+        want_absgrad = bool(getattr(rs, "absgrad", False)) and not infer and means2D is not None
+        ctx.absgrad_sink = means2D if want_absgrad else None
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg, view, proj, cam, radii, geom,
-                              img, holder.get("bin"), aux_c, scratch, feat_c, feat_out, dist_out, dist_tot)
+                              img, holder.get("bin"), aux_c, scratch, feat_c, feat_out, dist_out, dist_tot,
+                              *((color, depth) if want_absgrad else ()))
         ctx.scratch_fresh = scratch is not None  # (a second backward over this forward clears a scratch of its own)
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
@@ -730,7 +762,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch, feat,
-         feat_out, dist_out, dist_tot) = ctx.saved_tensors
+         feat_out, dist_out, dist_tot) = ctx.saved_tensors[:21]
+        sink = getattr(ctx, "absgrad_sink", None)
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
         grad_feat = grad_extra[int(want_alpha)] if has_feat else None
@@ -745,6 +778,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_color = _f32c(grad_color)
             grad_depth = _f32c(grad_depth)
             grad_alpha = _f32c(grad_alpha)   # (None: the default backward kernels)
+            absgrad_grads = (grad_color, grad_depth, grad_alpha)   # (what this backward was handed, before anything is added)
             if grad_dist is not None and grad_depth is None:   # ggr_backward carries the depth-value term on with a depth gradient
                 grad_depth = torch.zeros((H, W), dtype=torch.float32, device=dev)
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
@@ -767,6 +801,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             scratch = fwd_scratch if zeroed else torch.empty((lib.ggr_backward_scratch_bytes(P),), dtype=torch.uint8, device=dev)
 
             st = _settings_struct(rs, P, M, bg, view, proj, cam)
+            if sink is not None:   # Σ_pixels |∂L_pixel/∂mean2D| of the colour / depth / alpha loss (csrc/blend_absgrad.hip)
+                _means2d_absgrad(lib, st, None, geom, img, binb, ctx.num_rendered, *ctx.saved_tensors[21:23], *absgrad_grads,
+                                 (P,), sink, stream)
             d_feat = None
             if grad_feat is not None:   # the feature loss's terms first: they meet the colour's in the scratch records
                 d_feat = torch.empty_like(feat)
@@ -946,8 +983,11 @@ class _RasterizeViews(torch.autograd.Function):
                          shp(scales), shp(rotations), shp(cov3Ds_precomp))
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None,
                    means2D is not None)
+        want_absgrad = bool(getattr(rs, "absgrad", False)) and not infer and means2D is not None
+        ctx.absgrad_sink = means2D if want_absgrad else None
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg_c, view, proj, cam, radii, geom,
-                              img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out, dist_out, dist_tot)
+                              img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out, dist_out, dist_tot,
+                              *((color, depth) if want_absgrad else ()))
         ctx.scratch_fresh = scratch is not None
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
@@ -966,7 +1006,8 @@ class _RasterizeViews(torch.autograd.Function):
         lib = _lib.load()
         rs = ctx.raster_settings
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, tf, sc_in,
-         fwd_scratch, feat, feat_out, dist_out, dist_tot) = ctx.saved_tensors
+         fwd_scratch, feat, feat_out, dist_out, dist_tot) = ctx.saved_tensors[:23]
+        sink = getattr(ctx, "absgrad_sink", None)
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
         grad_feat = grad_extra[int(want_alpha)] if has_feat else None
@@ -980,6 +1021,7 @@ class _RasterizeViews(torch.autograd.Function):
             if grad_color is None:
                 grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
             grad_color, grad_depth, grad_alpha = _f32c(grad_color), _f32c(grad_depth), _f32c(grad_alpha)
+            absgrad_grads = (grad_color, grad_depth, grad_alpha)   # (what this backward was handed, before anything is added)
             if grad_dist is not None and grad_depth is None:   # ggr_backward_views carries the depth-value term on with a depth gradient
                 grad_depth = torch.zeros((V, H, W), dtype=torch.float32, device=dev)
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
@@ -1002,6 +1044,9 @@ class _RasterizeViews(torch.autograd.Function):
             st = _settings_struct(rs._replace(tanfovx=0.0, tanfovy=0.0, tanfov=None), P, M, None, None, None, None)
             vw = _lib.GgrViews(num_views=V, viewmatrix=view.data_ptr(), projmatrix=proj.data_ptr(), campos=cam.data_ptr(),
                                bg=bg.data_ptr(), tanfov=tf.data_ptr(), input_scale=_ptr(sc_in), num_sets=B)
+            if sink is not None:
+                _means2d_absgrad(lib, st, vw, geom, img, binb, ctx.num_rendered, *ctx.saved_tensors[23:25], *absgrad_grads,
+                                 (V, P), sink, stream)
             d_feat = None
             if grad_feat is not None:
                 d_feat = torch.empty_like(feat)
@@ -1079,6 +1124,9 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     if ((scales is None or rotations is None) and cov3D_precomp is None) or (
             (scales is not None or rotations is not None) and cov3D_precomp is not None):
         raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+    if bool(getattr(raster_settings, "absgrad", False)) and means2D is None:
+        raise ValueError("rasterize_views: raster_settings.absgrad=True needs the means2D argument ([V,P,3]): the backward sets "
+                         "means2D.absgrad on it")
     out = _RasterizeViews.apply(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                 viewmatrices, projmatrices, campos, aux_precomp, means2D, raster_settings, bg, tanfov,
                                 input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))

@@ -579,6 +579,56 @@ int ggr_distortion_forward(const GgrSettings* settings, const GgrViews* views /*
 int ggr_distortion_backward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrDistortionPass* pass,
                             void* stream);
 
+/* ---- the absgrad pass: per-Gaussian ABSOLUTE screen-space positional gradients over a forward's lists (ABI 11, additive) --------
+ * What a training loop's densification thresholds (AbsGS, GOF; gsplat's `absgrad`).  dL_dmeans2D of ggr_backward* is a sum over
+ * pixels of per-pixel terms that change sign across a Gaussian's footprint and cancel; this pass sums their absolute values.
+ * Per view, for a pixel p take the entries i the colour blend composited there (LIVE exactly as in the contribution pass above),
+ * in list order, with w_i = α_i·T_i the colour's own weight, bit for bit.  The loss reaches the pixel through the planes a
+ * forward blends, C = Σ w_i c_i + T_f·bg, D = Σ w_i d_i (d the DEPTH VALUE — what out_depth blends: view z, aux_precomp, or
+ * max(a + b·z/s, 0) under aux_affine) and A = 1 − T_f = Σ w_i, with upstream gradients g_C (dL_dout_color), g_D (dL_dout_depth)
+ * and g_A (dL_dout_alpha); g_D and g_A count as zero when the pointer is NULL.  With
+ *     u_i  = g_C·c_i + g_D·d_i + g_A              u_bg = g_C·bg
+ *     ∂L_p/∂α_i = T_i·u_i − ( Σ_{j behind i} w_j·u_j + T_f·u_bg ) / (1 − α_i)
+ *     gx_{i,p} = ½W · ∂L_p/∂α_i · o_i·G_i · ( −(cxx·dx + cxy·dy) )
+ *     gy_{i,p} = ½H · ∂L_p/∂α_i · o_i·G_i · ( −(cyy·dy + cxy·dx) )               (dx, dy) = mean2D_i − p
+ * — exactly the terms ggr_backward* sums into dL_dmeans2D[:, :2] (the 0.99 cap straight-through, the same NDC scaling, o_i the
+ * splat record's opacity: compensated under antialiasing) — the outputs are, per (view, Gaussian) row,
+ *     out_absgrad = ( Σ_p |gx_{i,p}| , Σ_p |gy_{i,p}| )         out_grad = ( Σ_p gx_{i,p} , Σ_p gy_{i,p} )    (a cross-check)
+ * Both are zero for a Gaussian no pixel composited.  A pixel whose g_C, g_D and g_A are all exactly zero contributes exactly
+ * nothing and takes no entry, so a gradient confined to a window of the frame, or a scissored frame, stays cheap.  The terms a
+ * FEATURE loss (ggr_features_backward) and a DISTORTION loss (ggr_distortion_backward) add to dL_dmeans2D are NOT part of
+ * absgrad: it covers what ggr_backward*'s own blend differentiates — colour, depth and alpha.  The sums are accumulated with
+ * float atomics: reproducible up to the order of their additions.
+ *
+ * Protocol, as the feature and distortion passes.  ggr_means2d_absgrad runs AFTER ggr_forward* (any variant, exact or sync-free
+ * mode) on the same stream, over the geom_buffer, image_buffer, binning_buffer (as the forward RETURNED it) and num_rendered of a
+ * forward that kept its backward state (not no_backward), any time before those buffers are released; out_color / out_depth are
+ * the planes that forward wrote (the per-pixel totals are taken from them; the background enters through out_color, so the
+ * settings' bg / GgrViews.bg are not read).  It is independent of ggr_backward* and does not touch the backward scratch.
+ * `views` NULL: one view; else the GgrViews of the launch set — only num_views / num_sets are read.  The call clears both
+ * outputs itself (hipMemsetAsync on `stream`) and so writes EVERY element; it allocates nothing, reads nothing back and is
+ * hipGraph-capturable.  num_points == 0, an empty frame or num_rendered == 0: 0 after the clearing.  GGR_E_INVALID, before
+ * anything is enqueued, for a struct_size smaller than the struct, a nonzero `reserved`, a negative size, or a NULL buffer /
+ * plane the call needs (out_depth may be NULL iff dL_dout_depth is). */
+typedef struct GgrAbsgradPass {
+    int32_t struct_size;            /* sizeof(GgrAbsgradPass) */
+    int32_t reserved;               /* 0 */
+    const void* geom_buffer;        /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;     /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;           /* the forward's (−1: sync-free mode) */
+    const float* out_color;         /* device [3,H,W] / [V,3,H,W]: the forward's colour plane(s) */
+    const float* out_depth;         /* device [H,W] / [V,H,W]: the forward's depth plane(s); may be NULL iff dL_dout_depth is NULL */
+    const float* dL_dout_color;     /* device [3,H,W] / [V,3,H,W] */
+    const float* dL_dout_depth;     /* device [H,W] / [V,H,W] or NULL */
+    const float* dL_dout_alpha;     /* device [H,W] / [V,H,W] or NULL */
+    float* out_absgrad;             /* device [P,2] / [V,P,2]; every element written */
+    float* out_grad;                /* same shape, or NULL */
+} GgrAbsgradPass;
+
+int ggr_means2d_absgrad(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrAbsgradPass* pass,
+                        void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
