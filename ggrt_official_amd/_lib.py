@@ -136,6 +136,20 @@ def pick_pass(**fields) -> GgrPickPass:
     return GgrPickPass(struct_size=C.sizeof(GgrPickPass), **fields)
 
 
+MAX_HITS = 32   # GGR_MAX_HITS
+
+
+class GgrHitPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("num_hits", C.c_int32), ("geom_buffer", C.c_void_p),
+                ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
+                ("out_index", C.c_void_p), ("out_weight", C.c_void_p), ("out_rest", C.c_void_p), ("out_count", C.c_void_p)]
+
+
+def hit_pass(**fields) -> GgrHitPass:
+    """The argument of ggr_pixel_hits (include/ggr_raster.h), struct_size filled in."""
+    return GgrHitPass(struct_size=C.sizeof(GgrHitPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -213,6 +227,7 @@ SYMBOLS = [
     ("ggr_features_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrFeaturePass), C.c_void_p]),
     ("ggr_contributions", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrContributionPass), C.c_void_p]),
     ("ggr_pixel_picks", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrPickPass), C.c_void_p]),
+    ("ggr_pixel_hits", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrHitPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

@@ -9,6 +9,7 @@
 #include "blend_feat.h"
 #include "blend_contrib.h"
 #include "blend_pick.h"
+#include "blend_hits.h"
 #include "blend_dist.h"
 #include "blend_absgrad.h"
 #include <algorithm>
@@ -1145,6 +1146,51 @@ int ggr_pixel_picks(const GgrSettings* st, const GgrViews* views, const GgrPickP
     ggr::launch_blend_pick(W, H, im.ranges, (const uint32_t*)pp->binning_buffer, g.splat, pp->out_median_index,
                            pp->out_median_depth, pp->out_max_index, pp->out_max_weight, pp->out_count, V, P1, scissored ? 1 : 0, s);
     KCHECK(st->debug != 0, s, "blend_pick");
+    return GGR_OK;
+}
+
+// ---- the hit pass (blend_hits.hip): per-pixel hit lists — the first K composited Gaussians, their weights, the rest, the count ---
+int ggr_pixel_hits(const GgrSettings* st, const GgrViews* views, const GgrHitPass* hp, void* stream) {
+    g_err[0] = 0;
+    if (!st || !hp) return fail(GGR_E_INVALID, "null settings / hit pass");
+    if (hp->struct_size < (int32_t)sizeof(GgrHitPass))
+        return fail(GGR_E_INVALID, "GgrHitPass.struct_size %d is smaller than the %d bytes of its fields", (int)hp->struct_size,
+                    (int)sizeof(GgrHitPass));
+    if (hp->num_hits < 1 || hp->num_hits > GGR_MAX_HITS)
+        return fail(GGR_E_INVALID, "GgrHitPass.num_hits must be 1..%d, not %d", GGR_MAX_HITS, (int)hp->num_hits);
+    if ((hp->out_index == nullptr) != (hp->out_weight == nullptr))
+        return fail(GGR_E_INVALID, "GgrHitPass: out_index and out_weight come as a pair (both, or neither)");
+    if (!hp->out_index && !hp->out_rest && !hp->out_count) return fail(GGR_E_INVALID, "GgrHitPass: every output is NULL");
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (!hp->geom_buffer || !hp->image_buffer) return fail(GGR_E_INVALID, "GgrHitPass: null geom / image buffer of the forward");
+    if (hp->num_rendered != 0 && !hp->binning_buffer) return fail(GGR_E_INVALID, "GgrHitPass.binning_buffer is NULL");
+    int V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        V = views->num_views;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height, K = hp->num_hits;
+    const size_t pixels = (size_t)V * (size_t)W * (size_t)H;
+    if (pixels == 0) return GGR_OK;
+    if (P1 == 0 || hp->num_rendered == 0) {   // no list entry anywhere: every element gets its padding value (−1 = all bits set)
+        if (hp->out_index) HIP_TRY(hipMemsetAsync(hp->out_index, 0xFF, pixels * K * sizeof(int32_t), s));
+        if (hp->out_weight) HIP_TRY(hipMemsetAsync(hp->out_weight, 0, pixels * K * sizeof(float), s));
+        if (hp->out_rest) HIP_TRY(hipMemsetAsync(hp->out_rest, 0, pixels * sizeof(float), s));
+        if (hp->out_count) HIP_TRY(hipMemsetAsync(hp->out_count, 0, pixels * sizeof(int32_t), s));
+        return GGR_OK;
+    }
+    GeomLayout g = ggr_carve_geom((void*)hp->geom_buffer, (size_t)V * (size_t)P1, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)hp->image_buffer, W, H, V);
+    const bool scissored = (st->scissor[0] | st->scissor[1] | st->scissor[2] | st->scissor[3]) != 0;
+    ggr::launch_blend_hits(W, H, im.ranges, (const uint32_t*)hp->binning_buffer, g.splat, K, hp->out_index, hp->out_weight,
+                           hp->out_rest, hp->out_count, V, P1, scissored ? 1 : 0, s);
+    KCHECK(st->debug != 0, s, "blend_hits");
     return GGR_OK;
 }
 

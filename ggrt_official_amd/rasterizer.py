@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import operator
 import os
 import threading
 from typing import NamedTuple, Optional
@@ -86,6 +87,19 @@ class _RasterizationSettingsFields(NamedTuple):
     #                         rasterize_views) as a 4th output, differentiable (include/ggr_raster.h GgrForwardExtra) — what
     #                         gsplat returns as `alphas`.  False: the 3-tuple as before, nothing extra allocated or written
 
+def _hits_setting(k) -> int:
+    """``return_hits`` as an int in [0, MAX_HITS]; raises on anything else (a bool among them: K is a number of slots)"""
+    try:
+        if isinstance(k, bool):
+            raise TypeError
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError(f"return_hits must be an integer number of slots K, 0 <= K <= {_lib.MAX_HITS}, not {k!r}") from None
+    if not 0 <= k <= _lib.MAX_HITS:
+        raise ValueError(f"return_hits must be 0 (off) or 1 <= K <= {_lib.MAX_HITS}, not {k}")
+    return k
+
+
 class GaussianRasterizationSettings(_RasterizationSettingsFields):
     """The settings tuple of the fields above — upstream's, then this project's extensions, positional construction and
     ``_fields`` as they always were — and ONE more setting behind them all that is kept beside the tuple:
@@ -117,13 +131,23 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
     caller passed, ``means2D.absgrad`` = Σ_pixels |∂L_pixel/∂mean2D| ([P,2]; [V,P,2] from ``rasterize_views``; float32, detached,
     overwritten by each backward) — gsplat's convention, what densification thresholds — and ``means2D.absgrad_signed``, the signed
     sums of the same terms (= ``means2D.grad[:, :2]`` of a colour / depth / alpha loss).  The terms of a feature or distortion
-    loss are not included.  False: nothing extra allocated, saved or called."""
+    loss are not included.  False: nothing extra allocated, saved or called.
+
+    ``return_hits`` (int K, default 0 = off; keyword only; 0 <= K <= 32), kept beside the tuple in the same way: also return, as
+    the VERY LAST output (behind the picks), a ``PixelHits(index, weight, rest, count)``: per pixel the first K entries the colour
+    blend composited there, in list order (front to back) — ``index`` int32 [K,H,W] (−1 behind the last one) and ``weight``
+    float32 [K,H,W] (w = α·T, the colour's own bits; 0 behind the last one) —, ``rest`` [H,W] = Σ w of the entries behind the
+    K-th, and ``count`` [H,W], the number of all of them (include/ggr_raster.h GgrHitPass); [V,…] from ``rasterize_views``.  Not
+    differentiable — ``composite_hits`` composites a differentiable per-Gaussian value over the slots.  0: nothing extra
+    allocated or called."""
     return_contributions = False   # (instances made by `_make` from the bare items)
     return_picks = False
     return_distortion = False
     absgrad = False
+    return_hits = 0
 
-    def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, absgrad=False, **kw):
+    def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, absgrad=False,
+                return_hits=0, **kw):
         n = len(_RasterizationSettingsFields._fields)
         if len(args) == n + 2:
             args, return_contributions, return_picks = args[:n], args[n], args[n + 1]
@@ -134,6 +158,7 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         self.return_picks = bool(return_picks)
         self.return_distortion = bool(return_distortion)
         self.absgrad = bool(absgrad)
+        self.return_hits = _hits_setting(return_hits)
         return self
 
     def _replace(self, **kw):
@@ -141,20 +166,22 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         picks = kw.pop("return_picks", self.return_picks)
         dist = kw.pop("return_distortion", self.return_distortion)
         absg = kw.pop("absgrad", self.absgrad)
+        hits = _hits_setting(kw.pop("return_hits", self.return_hits))
         new = super()._replace(**kw)
         new.return_contributions = bool(on)
         new.return_picks = bool(picks)
         new.return_distortion = bool(dist)
         new.absgrad = bool(absg)
+        new.return_hits = hits
         return new
 
     def _asdict(self):
-        return dict(super()._asdict(), absgrad=self.absgrad, return_distortion=self.return_distortion, return_contributions=self.return_contributions,
-                    return_picks=self.return_picks)
+        return dict(super()._asdict(), absgrad=self.absgrad, return_distortion=self.return_distortion, return_hits=self.return_hits,
+                    return_contributions=self.return_contributions, return_picks=self.return_picks)
 
     def __repr__(self):
         return (super().__repr__()[:-1] + f", absgrad={self.absgrad!r}, return_distortion={self.return_distortion!r}"
-                f", return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
+                f", return_hits={self.return_hits!r}, return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
 
 
 class Contributions(NamedTuple):
@@ -190,6 +217,38 @@ def pick_values(values: torch.Tensor, index: torch.Tensor, fill: float = 0.0) ->
     if values.dim() == 2:
         valid = valid.unsqueeze(-1)
     return torch.where(valid, got, torch.full((), fill, dtype=values.dtype, device=values.device))
+
+
+class PixelHits(NamedTuple):
+    """Per-pixel hit lists (``return_hits=K``): the first K list entries the colour blend composited at the pixel, in list order
+    (front to back), with their blend weights — [K,H,W] / [H,W] arrays, [V,K,H,W] / [V,H,W] from ``rasterize_views``.  Indices
+    are Gaussian indices in [0,P) within the view's Gaussian set.  Detached: they carry no gradient (``composite_hits``).  All
+    bit-reproducible: no atomic, ``rest`` is a per-pixel sum in list order."""
+    index: torch.Tensor    # int32 [K,H,W]: the k-th composited Gaussian, −1 for k >= count
+    weight: torch.Tensor   # float32 [K,H,W]: its blend weight w = α·T (the colour blend's bits), 0 for k >= count
+    rest: torch.Tensor     # float32 [H,W]: Σ w of the composited entries behind the K-th — what the slots leave out of alpha
+    count: torch.Tensor    # int32 [H,W]: the number of composited entries (all of them, not min(count, K))
+
+
+def composite_hits(values: torch.Tensor, hits: PixelHits) -> torch.Tensor:
+    """Σ_k weight[k]·values[index[k]] over the K slots of a ``PixelHits`` of ONE view ([K,H,W] arrays): per-Gaussian ``values``
+    ([P] or [P,C]) composited with the colour blend's own weights → [H,W] (+ [C]); padding slots contribute 0.  With
+    ``count <= K`` everywhere this is what the feature pass renders for the same values; elsewhere it leaves out the entries
+    that ``hits.rest`` sums up.  Differentiable in ``values`` (the weights are constants).  Pure torch; works on CPU tensors.
+    For the [V,K,H,W] arrays of a launch set call it per view (per Gaussian set), as ``pick_values``."""
+    if values.dim() not in (1, 2):
+        raise ValueError(f"composite_hits: values must be [P] or [P,C], not {tuple(values.shape)}")
+    index, weight = hits.index, hits.weight
+    if index.dim() != 3 or weight.shape != index.shape:
+        raise ValueError(f"composite_hits: hits.index / hits.weight must be [K,H,W] arrays of one view and of one shape, not "
+                         f"{tuple(index.shape)} / {tuple(weight.shape)}")
+    idx = index.to(device=values.device, dtype=torch.long)
+    w = weight.to(device=values.device, dtype=values.dtype)
+    w = torch.where(idx >= 0, w, torch.zeros((), dtype=w.dtype, device=w.device))   # (padding: 0 whatever it gathers)
+    got = values[idx.clamp(min=0)]
+    if values.dim() == 2:
+        w = w.unsqueeze(-1)
+    return (w * got).sum(0)
 
 
 class StageProfile:
@@ -308,6 +367,21 @@ def _pixel_picks(lib, st, vw, geom, img, binb, num_rendered, shape, dev, stream)
     return md, mi, xw, xi, cnt
 
 
+def _pixel_hits(lib, st, vw, geom, img, binb, num_rendered, k, shape, dev, stream):
+    """ggr_pixel_hits over the buffers of the forward that has just returned: index / weight of `shape[:-2] + (k,) + shape[-2:]`
+    and rest / count of `shape` ([H,W] / [V,H,W]), in `PixelHits`' order.  The call writes every element."""
+    slots = shape[:-2] + (k,) + shape[-2:]
+    idx = torch.empty(slots, dtype=torch.int32, device=dev)
+    wgt = torch.empty(slots, dtype=torch.float32, device=dev)
+    rest = torch.empty(shape, dtype=torch.float32, device=dev)
+    cnt = torch.empty(shape, dtype=torch.int32, device=dev)
+    hp = _lib.hit_pass(num_hits=int(k), geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
+                       num_rendered=int(num_rendered), out_index=idx.data_ptr(), out_weight=wgt.data_ptr(),
+                       out_rest=rest.data_ptr(), out_count=cnt.data_ptr())
+    _check(lib.ggr_pixel_hits(C.byref(st), _byref(vw), C.byref(hp), stream), "ggr_pixel_hits")
+    return idx, wgt, rest, cnt
+
+
 def _distortion_pass(geom, img, binb, num_rendered, plane, totals, **more):
     return _lib.distortion_pass(reserved=0, geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
                                 num_rendered=int(num_rendered), out_distortion=plane.data_ptr(), totals=_ptr(totals), **more)
@@ -349,12 +423,15 @@ def _means2d_absgrad(lib, st, vw, geom, img, binb, num_rendered, color, depth, g
     sink.absgrad_signed = signed
 
 
-def _with_contributions(out, on: bool, picks: bool = False):
-    """The public tuple: the three trailing arrays of a `return_contributions` call as ONE `Contributions` element — and the
-    five planes of a `return_picks` call, behind them, as ONE `PixelPicks` element, last."""
+def _with_contributions(out, on: bool, picks: bool = False, hits: bool = False):
+    """The public tuple: the three trailing arrays of a `return_contributions` call as ONE `Contributions` element — the five
+    planes of a `return_picks` call, behind them, as ONE `PixelPicks` element — and the four arrays of a `return_hits` call,
+    behind those, as ONE `PixelHits` element, last."""
     tail = ()
+    if hits:
+        out, tail = out[:-4], (PixelHits(*out[-4:]),)
     if picks:
-        out, tail = out[:-5], (PixelPicks(*out[-5:]),)
+        out, tail = out[:-5], (PixelPicks(*out[-5:]),) + tail
     if on:
         out = out[:-3] + (Contributions(*out[-3:]),)
     return out + tail
@@ -726,6 +803,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             picks = ()
             if bool(getattr(rs, "return_picks", False)):   # per-pixel picks over the same lists (csrc/blend_pick.hip)
                 picks = _pixel_picks(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, (H, W), dev, stream)
+            n_hits = int(getattr(rs, "return_hits", 0) or 0)
+            if n_hits:   # per-pixel hit lists over the same lists (csrc/blend_hits.hip); they ride behind the picks
+                picks += _pixel_hits(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (H, W), dev, stream)
 
         # exact mode: count known, nothing to keep.  Sync-free mode: count + flags live in the geometry buffer on the
         # device, so that (≈100 MB at P = 1 M) buffer stays referenced until this thread's next forward
@@ -767,7 +847,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
         grad_feat = grad_extra[int(want_alpha)] if has_feat else None
-        grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions' and picks' None)
+        grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions', picks' and hits' None)
         P, M, H, W = ctx.dims
         dev = means3D.device
         need_pose = any(ctx.needs_input_grad[8:11])
@@ -972,6 +1052,9 @@ class _RasterizeViews(torch.autograd.Function):
             picks = ()
             if bool(getattr(rs, "return_picks", False)):
                 picks = _pixel_picks(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, (V, H, W), dev, stream)
+            n_hits = int(getattr(rs, "return_hits", 0) or 0)
+            if n_hits:
+                picks += _pixel_hits(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (V, H, W), dev, stream)
         _tls.last_forward = (geom, P * V) if capacity > 0 else (None, int(fout.num_rendered))
         _tls.last_binning = (int(fout.depth_sort_used), int(fout.max_list_len))
         ctx.raster_settings = rs
@@ -1011,7 +1094,7 @@ class _RasterizeViews(torch.autograd.Function):
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
         grad_feat = grad_extra[int(want_alpha)] if has_feat else None
-        grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions' and picks' None)
+        grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions', picks' and hits' None)
         P, M, H, W, V, B = ctx.dims
         PT = P * B   # rows of the flat [B·P, …] gradient arrays
         dev = means3D.device
@@ -1115,8 +1198,10 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
     differentiable like the colour.  With ``raster_settings.return_contributions`` a ``Contributions`` of ``[V,P]`` tensors
     (Σ w, max w, pixel count per view and Gaussian; not differentiable) follows, and with ``raster_settings.return_picks`` a
     ``PixelPicks`` of ``[V,H,W]`` planes (median depth / index, dominant weight / index, contributor count per pixel; indices
-    within the view's Gaussian set; not differentiable) is the very last output.  With ``raster_settings.return_distortion``
-    the depth-distortion plane ``distortion [V,H,W]`` (differentiable) stands behind alpha and the features, in front of both."""
+    within the view's Gaussian set; not differentiable) is the very last output — but for ``raster_settings.return_hits = K``,
+    which puts a ``PixelHits`` (``index`` / ``weight`` ``[V,K,H,W]``, ``rest`` / ``count`` ``[V,H,W]``; not differentiable)
+    behind it.  With ``raster_settings.return_distortion`` the depth-distortion plane ``distortion [V,H,W]`` (differentiable)
+    stands behind alpha and the features, in front of all three."""
     shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
     scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
     if (shs is None) == (colors_precomp is None):
@@ -1131,7 +1216,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
                                 viewmatrices, projmatrices, campos, aux_precomp, means2D, raster_settings, bg, tanfov,
                                 input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))
     return _with_contributions(out, bool(getattr(raster_settings, "return_contributions", False)),
-                               bool(getattr(raster_settings, "return_picks", False)))
+                               bool(getattr(raster_settings, "return_picks", False)),
+                               bool(getattr(raster_settings, "return_hits", 0)))
 
 
 def camera_setup(extrinsics: torch.Tensor, intrinsics: torch.Tensor, near: torch.Tensor, far: torch.Tensor,
@@ -1203,7 +1289,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     out = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                     cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
                                     torch.is_grad_enabled(), _none_if_empty(features_precomp))
-    return _with_contributions(out, bool(getattr(rs, "return_contributions", False)), bool(getattr(rs, "return_picks", False)))
+    return _with_contributions(out, bool(getattr(rs, "return_contributions", False)), bool(getattr(rs, "return_picks", False)),
+                               bool(getattr(rs, "return_hits", 0)))
 
 
 class GaussianRasterizer(nn.Module):
@@ -1240,9 +1327,10 @@ class GaussianRasterizer(nn.Module):
         ``features [K,H,W]`` = Σ f·α·T (no background term) as its LAST element, differentiable.  With
         ``return_contributions=True`` in the settings a ``Contributions(weight_sum, weight_max, pixel_count)`` of [P] tensors
         follows behind everything else (not differentiable), and with ``return_picks=True`` a ``PixelPicks(median_depth,
-        median_index, max_weight, max_index, count)`` of [H,W] planes behind that (not differentiable; ``pick_values``).  With
-        ``return_distortion=True`` the depth-distortion plane ``distortion [H,W]`` (differentiable) stands behind alpha and the
-        features, in front of both."""
+        median_index, max_weight, max_index, count)`` of [H,W] planes behind that (not differentiable; ``pick_values``), and
+        with ``return_hits=K`` a ``PixelHits(index, weight, rest, count)`` ([K,H,W] / [H,W]; not differentiable;
+        ``composite_hits``) as the very last element.  With ``return_distortion=True`` the depth-distortion plane
+        ``distortion [H,W]`` (differentiable) stands behind alpha and the features, in front of all three."""
         shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
         scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):

@@ -35,7 +35,7 @@ from typing import Literal, Optional
 import torch
 from torch import Tensor, nn
 
-from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelPicks
+from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelHits, PixelPicks
 
 DepthRenderingMode = Literal["depth", "disparity", "relative_disparity", "log"]
 
@@ -87,6 +87,7 @@ class DecoderOutput:
     features: Optional[Tensor] = None  # [b, v, K, h, w]: Σ f·α·T of the per-Gaussian channels (…, gaussian_features=[b,g,K])
     contributions: Optional[Contributions] = None  # [b, v, g] tensors: Σ w, max w, pixel count (…, return_contributions=True)
     picks: Optional[PixelPicks] = None  # [b, v, h, w] planes: median depth / index, dominant weight / index, count (…, return_picks=True)
+    hits: Optional[PixelHits] = None  # index / weight [b, v, K, h, w], rest / count [b, v, h, w]: the first K composited Gaussians (…, return_hits=K)
 
 
 def get_fov(intrinsics: Tensor) -> Tensor:
@@ -174,7 +175,8 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,
-                       antialiasing=False, return_alpha=False, *, return_picks=False, return_contributions=False):
+                       antialiasing=False, return_alpha=False, *, return_hits=0, return_picks=False,
+                       return_contributions=False):
     """Everything ``render_cuda`` hands to the rasterizer, batched: a list of
     (GaussianRasterizationSettings, kwargs) per view.  Split out so the golden-vector tests can
     compare it with what the reference's call site produces.
@@ -222,7 +224,7 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
             sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}),
             **({"antialiasing": True} if antialiasing else {}), **({"return_alpha": True} if return_alpha else {}),
             **({"return_contributions": True} if return_contributions else {}),
-            **({"return_picks": True} if return_picks else {}))
+            **({"return_picks": True} if return_picks else {}), **({"return_hits": return_hits} if return_hits else {}))
         kwargs = dict(means3D=gaussian_means[i], shs=shs[i] if use_sh else None,
                       colors_precomp=None if use_sh else shs[i, :, 0, :],
                       opacities=gaussian_opacities[i, ..., None])
@@ -258,10 +260,22 @@ def _stack_picks(ps) -> PixelPicks:
     return PixelPicks(*(torch.stack([getattr(p, f) for p in ps]) for f in PixelPicks._fields))
 
 
-def _tail_index(want_contrib: bool, want_picks: bool):
-    """Where a rasterizer call's tuple has (the rendered features, the Contributions): the picks, when on, are its last
-    element, the contributions stand in front of them, the features in front of both"""
-    return -1 - int(want_contrib) - int(want_picks), -1 - int(want_picks)
+def _stack_hits(hs) -> PixelHits:
+    """Per-call `PixelHits` → one with a leading axis over the calls"""
+    return PixelHits(*(torch.stack([getattr(p, f) for p in hs]) for f in PixelHits._fields))
+
+
+def _tail_index(want_contrib: bool, want_picks: bool, want_hits: bool = False):
+    """Where a rasterizer call's tuple has (the rendered features, the Contributions): the hits, when on, are its last
+    element, the picks, when on, stand in front of them (`_pick_index`), the contributions in front of those, the features in
+    front of all three"""
+    back = int(bool(want_picks)) + int(bool(want_hits))
+    return -1 - int(bool(want_contrib)) - back, -1 - back
+
+
+def _pick_index(want_hits: bool) -> int:
+    """Where a rasterizer call's tuple has the PixelPicks: last, or in front of the PixelHits"""
+    return -1 - int(bool(want_hits))
 
 
 def _stack_contributions(cs) -> Contributions:
@@ -274,7 +288,8 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
                 scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                gaussian_features: Optional[Tensor] = None, *, return_picks: bool = False, return_contributions: bool = False):
+                gaussian_features: Optional[Tensor] = None, *, return_hits: int = 0, return_picks: bool = False,
+                return_contributions: bool = False):
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
 
@@ -294,13 +309,18 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     ``Contributions`` of ``[batch,g]`` tensors: per view and Gaussian Σ w, max w and the pixel count of the same pass.
 
     ``return_picks=True`` (extension; keyword-only): the tuple's VERY LAST element is a ``PixelPicks`` of ``[batch,h,w]``
-    planes: per pixel the median depth / index, the dominant weight / index and the contributor count of the same pass."""
+    planes: per pixel the median depth / index, the dominant weight / index and the contributor count of the same pass.
+
+    ``return_hits=K`` (extension; keyword-only, 1 <= K <= 32): a ``PixelHits`` behind even that — ``index`` / ``weight``
+    ``[batch,K,h,w]``, ``rest`` / ``count`` ``[batch,h,w]``: per pixel the first K composited Gaussians of the same pass."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing,
-                               return_alpha, return_picks=return_picks, return_contributions=return_contributions)
+                               return_alpha, return_picks=return_picks, return_contributions=return_contributions,
+                               return_hits=return_hits)
     outs = _rasterize_views(calls, features=gaussian_features)
-    fi, ci = _tail_index(return_contributions, return_picks)
+    fi, ci = _tail_index(return_contributions, return_picks, return_hits)
+    pi = _pick_index(return_hits)
     res = (torch.stack([o[0] for o in outs]),)
     if return_alpha:
         res += (torch.stack([o[3] for o in outs]),)
@@ -309,7 +329,9 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     if return_contributions:
         res += (_stack_contributions([o[ci] for o in outs]),)
     if return_picks:
-        res += (_stack_picks([o[-1] for o in outs]),)
+        res += (_stack_picks([o[pi] for o in outs]),)
+    if return_hits:
+        res += (_stack_hits([o[-1] for o in outs]),)
     return res if len(res) > 1 else res[0]
 
 
@@ -355,7 +377,7 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
                            gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
                            antialiasing: bool = False, return_alpha: bool = False,
-                           gaussian_features: Optional[Tensor] = None, *, return_picks: bool = False,
+                           gaussian_features: Optional[Tensor] = None, *, return_hits: int = 0, return_picks: bool = False,
                            return_contributions: bool = False):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
@@ -368,22 +390,26 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     [b,h,w] of the same pass as a third result with ``return_alpha=True``; with ``gaussian_features [b,g,K]`` the rendered
     ``features [b,K,h,w]`` of the same pass as the LAST result; with ``return_contributions=True`` a ``Contributions`` of
     ``[b,g]`` tensors behind everything else — except a ``PixelPicks`` of ``[b,h,w]`` planes, the very last result with
-    ``return_picks=True`` (keyword-only; its ``median_depth`` holds the depth pass's per-Gaussian value ``max(0.5 + C0·f(z), 0)``)."""
+    ``return_picks=True`` (keyword-only; its ``median_depth`` holds the depth pass's per-Gaussian value ``max(0.5 + C0·f(z), 0)``)
+    — and, with ``return_hits=K`` (keyword-only), a ``PixelHits`` (``[b,K,h,w]`` / ``[b,h,w]``) behind even that."""
     feat = depth_feature(extrinsics, gaussian_means, near, far, depth_mode)  # unscaled, as the reference
     aux = (0.5 + SH_C0 * feat).clamp(min=0.0)
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing, return_alpha,
-                               return_picks=return_picks, return_contributions=return_contributions)
+                               return_picks=return_picks, return_contributions=return_contributions, return_hits=return_hits)
     outs = _rasterize_views(calls, aux=aux, features=gaussian_features)
-    fi, ci = _tail_index(return_contributions, return_picks)
+    fi, ci = _tail_index(return_contributions, return_picks, return_hits)
+    pi = _pick_index(return_hits)
     planes = (0, 2, 3) if return_alpha else (0, 2)
     if gaussian_features is not None:
         planes += (fi,)
     res = tuple(torch.stack([o[k] for o in outs]) for k in planes)
     if return_contributions:
         res += (_stack_contributions([o[ci] for o in outs]),)
-    return res + (_stack_picks([o[-1] for o in outs]),) if return_picks else res
+    if return_picks:
+        res += (_stack_picks([o[pi] for o in outs]),)
+    return res + (_stack_hits([o[-1] for o in outs]),) if return_hits else res
 
 
 def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape,
@@ -391,7 +417,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
                        sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                       gaussian_features: Optional[Tensor] = None, *, return_picks: bool = False,
+                       gaussian_features: Optional[Tensor] = None, *, return_hits: int = 0, return_picks: bool = False,
                        return_contributions: bool = False):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
@@ -420,11 +446,14 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     with ``return_contributions=True`` a ``Contributions`` of ``[n,g]`` tensors (per view and Gaussian Σ w, max w, pixel
     count of the same launch sets; not differentiable) behind everything else — except, with ``return_picks=True`` (keyword-only),
     a ``PixelPicks`` of ``[n,h,w]`` planes (per pixel the median depth / index, the dominant weight / index and the contributor
-    count of the same launch sets; indices within the view's batch element; not differentiable), the very last result."""
+    count of the same launch sets; indices within the view's batch element; not differentiable), the very last result — but for
+    ``return_hits=K`` (keyword-only, 1 <= K <= 32), which puts a ``PixelHits`` behind it: ``index`` / ``weight`` ``[n,K,h,w]``,
+    ``rest`` / ``count`` ``[n,h,w]``, per pixel the first K composited Gaussians of the same launch sets (not differentiable)."""
     n = extrinsics.shape[0]
     has_feat = gaussian_features is not None
-    want_contrib, want_picks = bool(return_contributions), bool(return_picks)
-    fi, ci = _tail_index(want_contrib, want_picks)   # where a rasterizer call's tuple has the rendered features / contributions
+    want_contrib, want_picks, n_hits = bool(return_contributions), bool(return_picks), int(return_hits)
+    fi, ci = _tail_index(want_contrib, want_picks, n_hits)   # where a rasterizer call's tuple has the rendered features / contributions
+    pi = _pick_index(n_hits)                                  # … and the picks
     h, w = image_shape
     d_sh = gaussians.harmonics.shape[-1]
     degree = isqrt(d_sh) - 1
@@ -474,7 +503,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[0], projmatrix=full[0], sh_degree=degree, campos=campos[0], prefiltered=False,
             list_capacity=list_capacity * n, sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
         out = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
@@ -482,7 +511,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                               features_precomp=gaussian_features, **kw)
         return _fused_result(out[0], out[2] if depth_mode is not None else None, out[3] if return_alpha else None,
                              return_alpha, out[fi] if has_feat else None, out[ci] if want_contrib else None,
-                                 out[-1] if want_picks else None)
+                                 out[pi] if want_picks else None, out[-1] if n_hits else None)
     # batch element b of every Gaussian tensor WITHOUT `t[b]`: select's backward zero-fills a full [B,…] tensor
     # and copies the slice in, per view (0.2 ms per view for 1 M × 25 SH coefficients).  One unbind per tensor
     # (backward = one stack) — or a free reshape when there is a single batch element, GGRt's case.
@@ -494,6 +523,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                                   per_batch(gaussians.harmonics), per_batch(gaussians.opacities))
     g_scales, g_rot, g_feat = per_batch(gaussians.scales), per_batch(gaussians.rotations), per_batch(gaussian_features)
     colors, depths, alphas, feats, contribs, picks = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+    hits = [None] * n
     groups = {}
     for i in range(n):
         groups.setdefault(int(view_to_batch[i]), []).append(i)
@@ -520,7 +550,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[idx[0]], projmatrix=full[idx[0]], sh_degree=degree, campos=campos[idx[0]],
             prefiltered=False, list_capacity=list_capacity * len(idx), sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         out = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
                               take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
@@ -530,7 +560,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         if len(idx) == n and contiguous:  # every view in this one launch set: hand its outputs on as they are
             return _fused_result(col, dep if depth_mode is not None else None, out[3] if return_alpha else None,
                                  return_alpha, out[fi] if has_feat else None, out[ci] if want_contrib else None,
-                                 out[-1] if want_picks else None)
+                                 out[pi] if want_picks else None, out[-1] if n_hits else None)
         for k, i in enumerate(idx):
             colors[i], depths[i] = col[k], dep[k]
             if has_feat:
@@ -538,7 +568,9 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             if want_contrib:
                 contribs[i] = Contributions(*(t[k] for t in out[ci]))
             if want_picks:
-                picks[i] = PixelPicks(*(t[k] for t in out[-1]))
+                picks[i] = PixelPicks(*(t[k] for t in out[pi]))
+            if n_hits:
+                hits[i] = PixelHits(*(t[k] for t in out[-1]))
             if return_alpha:
                 alphas[i] = out[3][k]
     for i in single:
@@ -557,7 +589,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             input_scale=None if scale is None else scale[i:i + 1], sh_channel_major=True, aux_affine=aux_affine,
             tanfov=None if tanfov is None else tanfov[i], sh_max_degree=sh_cap,
             scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
         means = g_means[b]
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
@@ -570,7 +602,9 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         if want_contrib:
             contribs[i] = out[ci]
         if want_picks:
-            picks[i] = out[-1]
+            picks[i] = out[pi]
+        if n_hits:
+            hits[i] = out[-1]
         if return_alpha:
             alphas[i] = out[3]
     # one view (GGRt's usual call): a view of the rasterizer's output instead of a stack — no copy kernel forward,
@@ -578,18 +612,22 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     stack = lambda ts: ts[0].unsqueeze(0) if len(ts) == 1 else torch.stack(ts)
     return _fused_result(stack(colors), stack(depths) if depth_mode is not None else None,
                          stack(alphas) if return_alpha else None, return_alpha, stack(feats) if has_feat else None,
-                         _stack_contributions(contribs) if want_contrib else None, _stack_picks(picks) if want_picks else None)
+                         _stack_contributions(contribs) if want_contrib else None, _stack_picks(picks) if want_picks else None,
+                         _stack_hits(hits) if n_hits else None)
 
 
-def _fused_result(color, depth, alpha, return_alpha, features=None, contributions=None, picks=None):
+def _fused_result(color, depth, alpha, return_alpha, features=None, contributions=None, picks=None, hits=None):
     """render_views_fused's result: (color, depth) as always, (color, depth, alpha) with return_alpha; the rendered feature
-    channels, when asked for, come behind them, the contributions, when asked for, behind those, and the picks last"""
+    channels, when asked for, come behind them, the contributions, when asked for, behind those, then the picks, and the
+    hits last"""
     res = (color, depth, alpha) if return_alpha else (color, depth)
     if features is not None:
         res += (features,)
     if contributions is not None:
         res += (contributions,)
-    return res if picks is None else res + (picks,)
+    if picks is not None:
+        res += (picks,)
+    return res if hits is None else res + (hits,)
 
 
 def contribution_keep_mask(contributions: Contributions, min_weight_max: Optional[float] = None,
@@ -655,7 +693,7 @@ class DecoderSplattingCUDA(nn.Module):
     def forward(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                 image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None,
                 return_alpha: bool = False, gaussian_features: Optional[Tensor] = None,
-                *, return_picks: bool = False, return_contributions: bool = False) -> DecoderOutput:
+                *, return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False) -> DecoderOutput:
         """``scissor=(x0, y0, x1, y1)`` (extension, fused path): render only that pixel window's tiles — the
         deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``.  ``return_alpha=True`` (extension): the output's
         ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it.
@@ -665,15 +703,20 @@ class DecoderSplattingCUDA(nn.Module):
         Gaussian Σ w, max w and the pixel count of the colour pass (``contribution_keep_mask`` turns them into a pruning mask).
         ``return_picks=True`` (extension; keyword-only): the output's ``picks`` holds [b,v,h,w] planes — per pixel the median depth
         and its Gaussian, the dominant blend weight and its Gaussian (indices within the batch element's g Gaussians, −1 where
-        nothing was composited) and the contributor count of the colour pass; not differentiable (``pick_values``)."""
+        nothing was composited) and the contributor count of the colour pass; not differentiable (``pick_values``).
+        ``return_hits=K`` (extension; keyword-only, 1 <= K <= 32): the output's ``hits`` holds ``index`` / ``weight`` [b,v,K,h,w]
+        and ``rest`` / ``count`` [b,v,h,w] — per pixel the first K Gaussians the colour pass composited, front to back, with
+        their blend weights; not differentiable (``composite_hits``, per view)."""
         b, v = extrinsics.shape[:2]
         alpha = None
         has_feat = gaussian_features is not None
-        want_contrib, want_picks = bool(return_contributions), bool(return_picks)
-        fi, ci = _tail_index(want_contrib, want_picks)
+        want_contrib, want_picks, n_hits = bool(return_contributions), bool(return_picks), int(return_hits)
+        fi, ci = _tail_index(want_contrib, want_picks, n_hits)
+        pi = _pick_index(n_hits)
         unflat = lambda t: t.reshape(b, v, *t.shape[1:])
         unflat_c = lambda out: Contributions(*(unflat(t) for t in out[ci])) if want_contrib else None
-        unflat_p = lambda out: PixelPicks(*(unflat(t) for t in out[-1])) if want_picks else None
+        unflat_p = lambda out: PixelPicks(*(unflat(t) for t in out[pi])) if want_picks else None
+        unflat_h = lambda out: PixelHits(*(unflat(t) for t in out[-1])) if n_hits else None
         if scissor is not None and not (self.fused_inputs and self.fused_depth):
             raise ValueError("scissor needs the fused call site (fused_inputs and fused_depth)")
         bg = self.background_color.to(far.device)[None].expand(b * v, 3)
@@ -683,13 +726,13 @@ class DecoderSplattingCUDA(nn.Module):
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
                 scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
-                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks)
+                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]),
                                  None if depth is None else depth.reshape(b, v, *depth.shape[1:]), alpha,
-                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out))
+                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out), unflat_h(out))
         if depth_mode is not None and self.fused_depth:
             out = render_color_and_depth(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
@@ -697,21 +740,23 @@ class DecoderSplattingCUDA(nn.Module):
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
                 sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
                 gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                return_picks=want_picks, **self._ellipsoids(gaussians, v))
+                return_picks=want_picks, return_hits=n_hits, **self._ellipsoids(gaussians, v))
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]), alpha,
-                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out))
+                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out), unflat_h(out))
         color = render_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                             image_shape, bg, self._per_view(gaussians.means, v),
                             self._opt_per_view(gaussians.covariances, v), self._per_view(gaussians.harmonics, v),
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
                             antialiasing=self.antialiasing, return_alpha=return_alpha,
                             gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                            return_picks=want_picks, **self._ellipsoids(gaussians, v))
-        features, contributions, picks = None, None, None
-        if want_picks:   # (the last element; what is left is the result without it)
+                            return_picks=want_picks, return_hits=n_hits, **self._ellipsoids(gaussians, v))
+        features, contributions, picks, hits = None, None, None, None
+        if n_hits:   # (the last element; what is left is the result without it)
+            color, hits = (color[:-1] if len(color) > 2 else color[0]), PixelHits(*(unflat(t) for t in color[-1]))
+        if want_picks:   # (then the picks)
             color, picks = (color[:-1] if len(color) > 2 else color[0]), PixelPicks(*(unflat(t) for t in color[-1]))
         if want_contrib:   # (then the contributions)
             color, contributions = (color[:-1] if len(color) > 2 else color[0]), Contributions(*(unflat(t) for t in color[-1]))
@@ -723,7 +768,7 @@ class DecoderSplattingCUDA(nn.Module):
         color = color.reshape(b, v, *color.shape[1:])
         depth = None if depth_mode is None else self.render_depth(gaussians, extrinsics, intrinsics, near, far,
                                                                   image_shape, depth_mode)
-        return DecoderOutput(color, depth, alpha, features, contributions, picks)
+        return DecoderOutput(color, depth, alpha, features, contributions, picks, hits)
 
     def render_depth(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                      image_shape, mode: DepthRenderingMode = "depth") -> Tensor:

@@ -629,6 +629,52 @@ typedef struct GgrAbsgradPass {
 int ggr_means2d_absgrad(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrAbsgradPass* pass,
                         void* stream);
 
+/* ---- the hit pass: per-PIXEL hit lists over a forward's lists (ABI 11, additive) -------------------------------------------------
+ * Which Gaussians a pixel composited, in order, and with what weight — the pixel ↔ Gaussian association that a pick (one index,
+ * no ordering) cannot give.  For a pixel, walk its tile's list in order (front to back) with the colour blend's rules.  An entry
+ * is LIVE at the pixel exactly as in the contribution and pick passes above: power <= 0, α >= 1/255 after the 0.99 cap (the
+ * compensated opacity's α under antialiasing), and in front of the entry that would take T below 1e-4.  w = α·T_before is the
+ * colour's own weight, bit for bit.  With K = num_hits (1..GGR_MAX_HITS), for one view ([V,…] in front for a launch set):
+ *     out_index  int32   [K,H,W]  the id of the k-th live entry                                  (k >= count: −1)
+ *     out_weight float32 [K,H,W]  that entry's w                                                 (k >= count: 0)
+ *     out_rest   float32 [H,W]    Σ w of the live entries BEHIND the K-th, summed in list order: what the K slots leave out of
+ *                                 alpha                                                          (count <= K: 0)
+ *     out_count  int32   [H,W]    the number of live entries — all of them, not min(count, K)    (no live entry: 0)
+ * Ids are Gaussian indices in [0,P) WITHIN THE VIEW'S GAUSSIAN SET (the list id, a row of the [V·P] arrays, minus view·P), as in
+ * the pick pass.  Pixels of tiles outside the scissor window, and of frames with num_rendered == 0, get the padding values.  The
+ * call writes EVERY element of every requested array: the caller clears nothing.  Forward only: the arrays are not
+ * differentiable (a gradient through `weight` would be a backward pass of its own over the lists).  No atomic and no cross-lane
+ * sum: out_rest is a per-pixel sum in list order, so all four arrays are bit-identical from run to run, across the forms of the
+ * depth sort, across reference_rects and between a training and a no_backward forward.
+ * Relation to the other outputs: Σ_k out_weight + out_rest == alpha up to the rounding of the two summation orders; out_count
+ * is GgrPickPass.out_count; the largest out_weight of a pixel with count <= K is out_max_weight and the earliest slot that holds
+ * it is out_max_index; over the pixels with count <= K, the per-Gaussian number of slots that name a Gaussian is
+ * GgrContributionPass.out_pixel_count, their summed weight out_weight_sum and their largest out_weight_max.
+ *
+ * Protocol, limits and validation, as ggr_pixel_picks: ggr_pixel_hits runs AFTER ggr_forward* (any variant, any mode) on the same
+ * stream, over that forward's geom_buffer, image_buffer, binning_buffer (as the forward RETURNED it) and num_rendered (−1 in the
+ * sync-free mode); a no_backward forward's smaller buffers serve as well.  `views` NULL: one view; else the GgrViews of the launch
+ * set — only num_views / num_sets are read.  It allocates nothing, reads nothing back and is hipGraph-capturable.  out_index and
+ * out_weight come as a PAIR (both, or neither); out_rest and out_count may each be NULL (not computed); with both of them NULL a
+ * pixel is finished once it holds K entries (the walk ends earlier; out_index / out_weight keep every byte).  GGR_E_INVALID, before
+ * anything is enqueued, for a struct_size smaller than the struct, num_hits outside 1..GGR_MAX_HITS, exactly one of out_index /
+ * out_weight NULL, all four outputs NULL, or a NULL buffer the call needs. */
+#define GGR_MAX_HITS 32
+typedef struct GgrHitPass {
+    int32_t struct_size;            /* sizeof(GgrHitPass) */
+    int32_t num_hits;               /* K, 1..GGR_MAX_HITS */
+    const void* geom_buffer;        /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;     /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;           /* the forward's (−1: sync-free mode) */
+    int32_t* out_index;             /* device [K,H,W] / [V,K,H,W] or NULL (together with out_weight) */
+    float* out_weight;              /* device [K,H,W] / [V,K,H,W] or NULL (together with out_index) */
+    float* out_rest;                /* device [H,W] / [V,H,W] or NULL */
+    int32_t* out_count;             /* device [H,W] / [V,H,W] or NULL */
+} GgrHitPass;
+
+int ggr_pixel_hits(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrHitPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
