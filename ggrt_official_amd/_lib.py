@@ -150,6 +150,18 @@ def hit_pass(**fields) -> GgrHitPass:
     return GgrHitPass(struct_size=C.sizeof(GgrHitPass), **fields)
 
 
+class GgrHitGradPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("num_hits", C.c_int32), ("geom_buffer", C.c_void_p),
+                ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
+                ("weight", C.c_void_p), ("rest", C.c_void_p), ("count", C.c_void_p), ("dL_dweight", C.c_void_p),
+                ("dL_drest", C.c_void_p), ("scratch", C.c_void_p), ("scratch_zeroed", C.c_int32), ("reserved", C.c_int32)]
+
+
+def hit_grad_pass(**fields) -> GgrHitGradPass:
+    """The argument of ggr_pixel_hits_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrHitGradPass(struct_size=C.sizeof(GgrHitGradPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -228,6 +240,7 @@ SYMBOLS = [
     ("ggr_contributions", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrContributionPass), C.c_void_p]),
     ("ggr_pixel_picks", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrPickPass), C.c_void_p]),
     ("ggr_pixel_hits", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrHitPass), C.c_void_p]),
+    ("ggr_pixel_hits_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrHitGradPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

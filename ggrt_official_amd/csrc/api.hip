@@ -10,6 +10,7 @@
 #include "blend_contrib.h"
 #include "blend_pick.h"
 #include "blend_hits.h"
+#include "blend_hits_grad.h"
 #include "blend_dist.h"
 #include "blend_absgrad.h"
 #include <algorithm>
@@ -1191,6 +1192,46 @@ int ggr_pixel_hits(const GgrSettings* st, const GgrViews* views, const GgrHitPas
     ggr::launch_blend_hits(W, H, im.ranges, (const uint32_t*)hp->binning_buffer, g.splat, K, hp->out_index, hp->out_weight,
                            hp->out_rest, hp->out_count, V, P1, scissored ? 1 : 0, s);
     KCHECK(st->debug != 0, s, "blend_hits");
+    return GGR_OK;
+}
+
+// ---- the hit pass's backward (blend_hits_grad.hip): a loss over the hit weights and the rest, into the backward scratch ---------
+int ggr_pixel_hits_backward(const GgrSettings* st, const GgrViews* views, const GgrHitGradPass* hp, void* stream) {
+    g_err[0] = 0;
+    if (!st || !hp) return fail(GGR_E_INVALID, "null settings / hit gradient pass");
+    if (hp->struct_size < (int32_t)sizeof(GgrHitGradPass))
+        return fail(GGR_E_INVALID, "GgrHitGradPass.struct_size %d is smaller than the %d bytes of its fields", (int)hp->struct_size,
+                    (int)sizeof(GgrHitGradPass));
+    if (hp->reserved != 0) return fail(GGR_E_INVALID, "GgrHitGradPass.reserved must be 0, not %d", (int)hp->reserved);
+    if (hp->num_hits < 1 || hp->num_hits > GGR_MAX_HITS)
+        return fail(GGR_E_INVALID, "GgrHitGradPass.num_hits must be 1..%d, not %d", GGR_MAX_HITS, (int)hp->num_hits);
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (!hp->dL_dweight && !hp->dL_drest) return fail(GGR_E_INVALID, "GgrHitGradPass: dL_dweight and dL_drest are both NULL");
+    if (!hp->geom_buffer || !hp->image_buffer) return fail(GGR_E_INVALID, "GgrHitGradPass: null geom / image buffer of the forward");
+    if (hp->num_rendered != 0 && !hp->binning_buffer) return fail(GGR_E_INVALID, "GgrHitGradPass.binning_buffer is NULL");
+    if (!hp->weight) return fail(GGR_E_INVALID, "GgrHitGradPass.weight is NULL");
+    if (!hp->count) return fail(GGR_E_INVALID, "GgrHitGradPass.count is NULL");
+    if (!hp->scratch) return fail(GGR_E_INVALID, "GgrHitGradPass.scratch is NULL");
+    int V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        if ((int64_t)views->num_views * (int64_t)tiles_of(st->image_width, st->image_height) > (1 << 24))
+            return fail(GGR_E_LIMIT, "more than 2^24 tiles over all views");
+        V = views->num_views;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points, W = st->image_width, H = st->image_height;
+    BwdScratch sc = ggr_carve_bwd(hp->scratch, (size_t)P1, (size_t)V);
+    if (!hp->scratch_zeroed) HIP_TRY(hipMemsetAsync(hp->scratch, 0, sc.bytes, s));
+    if (P1 == 0 || hp->num_rendered == 0 || (size_t)W * H == 0) return GGR_OK;
+    GeomLayout g = ggr_carve_geom((void*)hp->geom_buffer, (size_t)P1 * V, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ImageLayout im = ggr_carve_image((void*)hp->image_buffer, W, H, V);
+    ggr::launch_blend_hits_bwd(W, H, im.ranges, (const uint32_t*)hp->binning_buffer, g.splat, im.final_T, hp->num_hits, hp->weight,
+                               hp->count, hp->dL_dweight, hp->dL_drest, sc.grad2d, V, s);
+    KCHECK(st->debug != 0, s, "blend_hits_bwd");
     return GGR_OK;
 }
 

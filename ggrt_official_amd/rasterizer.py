@@ -100,6 +100,14 @@ def _hits_setting(k) -> int:
     return k
 
 
+def _hits_grad_setting(on, k: int) -> bool:
+    """``hits_grad`` as a bool; raises when it is on without any hit slots to differentiate (``return_hits`` = `k` = 0)"""
+    on = bool(on)
+    if on and k < 1:
+        raise ValueError("hits_grad=True needs return_hits >= 1: there are no hit weights to differentiate")
+    return on
+
+
 class GaussianRasterizationSettings(_RasterizationSettingsFields):
     """The settings tuple of the fields above — upstream's, then this project's extensions, positional construction and
     ``_fields`` as they always were — and ONE more setting behind them all that is kept beside the tuple:
@@ -138,16 +146,24 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
     blend composited there, in list order (front to back) — ``index`` int32 [K,H,W] (−1 behind the last one) and ``weight``
     float32 [K,H,W] (w = α·T, the colour's own bits; 0 behind the last one) —, ``rest`` [H,W] = Σ w of the entries behind the
     K-th, and ``count`` [H,W], the number of all of them (include/ggr_raster.h GgrHitPass); [V,…] from ``rasterize_views``.  Not
-    differentiable — ``composite_hits`` composites a differentiable per-Gaussian value over the slots.  0: nothing extra
-    allocated or called."""
+    differentiable unless ``hits_grad`` is on — ``composite_hits`` composites a differentiable per-Gaussian value over the slots.
+    0: nothing extra allocated or called.
+
+    ``hits_grad`` (bool, default False; keyword only; needs ``return_hits >= 1``), kept beside the tuple in the same way: with grad
+    enabled, ``PixelHits.weight`` and ``PixelHits.rest`` come out DIFFERENTIABLE — a loss computed in torch over the slots (label
+    cross-entropy on ``composite_hits``, a penalty on ``rest``, …) then reaches opacities, means, covariances / scales / rotations
+    and the camera through a backward pass of its own over the lists (include/ggr_raster.h GgrHitGradPass); ``index`` and ``count``
+    stay non-differentiable.  The values are the same bits.  ``absgrad`` does not include these terms.  False, or under
+    ``torch.no_grad()``: exactly as without it — nothing extra allocated, saved or called."""
     return_contributions = False   # (instances made by `_make` from the bare items)
     return_picks = False
     return_distortion = False
     absgrad = False
     return_hits = 0
+    hits_grad = False
 
     def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, absgrad=False,
-                return_hits=0, **kw):
+                return_hits=0, hits_grad=False, **kw):
         n = len(_RasterizationSettingsFields._fields)
         if len(args) == n + 2:
             args, return_contributions, return_picks = args[:n], args[n], args[n + 1]
@@ -159,6 +175,7 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         self.return_distortion = bool(return_distortion)
         self.absgrad = bool(absgrad)
         self.return_hits = _hits_setting(return_hits)
+        self.hits_grad = _hits_grad_setting(hits_grad, self.return_hits)
         return self
 
     def _replace(self, **kw):
@@ -167,21 +184,23 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         dist = kw.pop("return_distortion", self.return_distortion)
         absg = kw.pop("absgrad", self.absgrad)
         hits = _hits_setting(kw.pop("return_hits", self.return_hits))
+        hgrad = _hits_grad_setting(kw.pop("hits_grad", self.hits_grad), hits)
         new = super()._replace(**kw)
         new.return_contributions = bool(on)
         new.return_picks = bool(picks)
         new.return_distortion = bool(dist)
         new.absgrad = bool(absg)
         new.return_hits = hits
+        new.hits_grad = hgrad
         return new
 
     def _asdict(self):
         return dict(super()._asdict(), absgrad=self.absgrad, return_distortion=self.return_distortion, return_hits=self.return_hits,
-                    return_contributions=self.return_contributions, return_picks=self.return_picks)
+                    hits_grad=self.hits_grad, return_contributions=self.return_contributions, return_picks=self.return_picks)
 
     def __repr__(self):
         return (super().__repr__()[:-1] + f", absgrad={self.absgrad!r}, return_distortion={self.return_distortion!r}"
-                f", return_hits={self.return_hits!r}, return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
+                f", return_hits={self.return_hits!r}, hits_grad={self.hits_grad!r}, return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
 
 
 class Contributions(NamedTuple):
@@ -222,7 +241,9 @@ def pick_values(values: torch.Tensor, index: torch.Tensor, fill: float = 0.0) ->
 class PixelHits(NamedTuple):
     """Per-pixel hit lists (``return_hits=K``): the first K list entries the colour blend composited at the pixel, in list order
     (front to back), with their blend weights — [K,H,W] / [H,W] arrays, [V,K,H,W] / [V,H,W] from ``rasterize_views``.  Indices
-    are Gaussian indices in [0,P) within the view's Gaussian set.  Detached: they carry no gradient (``composite_hits``).  All
+    are Gaussian indices in [0,P) within the view's Gaussian set.  Detached by default: they carry no gradient
+    (``composite_hits``).  With ``hits_grad=True`` in the settings (and grad enabled) ``weight`` and ``rest`` are differentiable:
+    a loss over them reaches opacities, means, covariances and the camera; ``index`` and ``count`` never carry one.  All
     bit-reproducible: no atomic, ``rest`` is a per-pixel sum in list order."""
     index: torch.Tensor    # int32 [K,H,W]: the k-th composited Gaussian, −1 for k >= count
     weight: torch.Tensor   # float32 [K,H,W]: its blend weight w = α·T (the colour blend's bits), 0 for k >= count
@@ -234,7 +255,8 @@ def composite_hits(values: torch.Tensor, hits: PixelHits) -> torch.Tensor:
     """Σ_k weight[k]·values[index[k]] over the K slots of a ``PixelHits`` of ONE view ([K,H,W] arrays): per-Gaussian ``values``
     ([P] or [P,C]) composited with the colour blend's own weights → [H,W] (+ [C]); padding slots contribute 0.  With
     ``count <= K`` everywhere this is what the feature pass renders for the same values; elsewhere it leaves out the entries
-    that ``hits.rest`` sums up.  Differentiable in ``values`` (the weights are constants).  Pure torch; works on CPU tensors.
+    that ``hits.rest`` sums up.  Differentiable in ``values`` — and in the weights as well when ``hits`` comes from a call with
+    ``hits_grad=True`` (they then carry a graph; otherwise they are constants).  Pure torch; works on CPU tensors.
     For the [V,K,H,W] arrays of a launch set call it per view (per Gaussian set), as ``pick_values``."""
     if values.dim() not in (1, 2):
         raise ValueError(f"composite_hits: values must be [P] or [P,C], not {tuple(values.shape)}")
@@ -380,6 +402,17 @@ def _pixel_hits(lib, st, vw, geom, img, binb, num_rendered, k, shape, dev, strea
                        out_rest=rest.data_ptr(), out_count=cnt.data_ptr())
     _check(lib.ggr_pixel_hits(C.byref(st), _byref(vw), C.byref(hp), stream), "ggr_pixel_hits")
     return idx, wgt, rest, cnt
+
+
+def _pixel_hits_backward(lib, st, vw, geom, img, binb, num_rendered, k, weight, rest, count, grad_weight, grad_rest, scratch,
+                         zeroed, stream):
+    """ggr_pixel_hits_backward: the terms of a loss over the hit weights / the rest go into `scratch` ahead of ggr_backward*, which
+    is then told that the scratch is in use (scratch_zeroed = 1).  `grad_weight` / `grad_rest`: None = no gradient (NULL)."""
+    hp = _lib.hit_grad_pass(num_hits=int(k), geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
+                            num_rendered=int(num_rendered), weight=weight.data_ptr(), rest=rest.data_ptr(),
+                            count=count.data_ptr(), dL_dweight=_ptr(grad_weight), dL_drest=_ptr(grad_rest),
+                            scratch=scratch.data_ptr(), scratch_zeroed=int(zeroed), reserved=0)
+    _check(lib.ggr_pixel_hits_backward(C.byref(st), _byref(vw), C.byref(hp), stream), "ggr_pixel_hits_backward")
 
 
 def _distortion_pass(geom, img, binb, num_rendered, plane, totals, **more):
@@ -805,7 +838,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 picks = _pixel_picks(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, (H, W), dev, stream)
             n_hits = int(getattr(rs, "return_hits", 0) or 0)
             if n_hits:   # per-pixel hit lists over the same lists (csrc/blend_hits.hip); they ride behind the picks
-                picks += _pixel_hits(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (H, W), dev, stream)
+                hits = _pixel_hits(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (H, W), dev, stream)
+                picks += hits
 
         # exact mode: count known, nothing to keep.  Sync-free mode: count + flags live in the geometry buffer on the
         # device, so that (≈100 MB at P = 1 M) buffer stays referenced until this thread's next forward
@@ -820,10 +854,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
         # absgrad: the backward takes the per-pixel totals from the colour and depth planes, and writes to the caller's means2D
         want_absgrad = bool(getattr(rs, "absgrad", False)) and not infer and means2D is not None
+        # hits_grad: weight and rest leave as differentiable outputs; the backward replays the lists over what the hit pass wrote
+        hits_grad = bool(n_hits) and bool(getattr(rs, "hits_grad", False)) and not infer
         ctx.absgrad_sink = means2D if want_absgrad else None
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg, view, proj, cam, radii, geom,
                               img, holder.get("bin"), aux_c, scratch, feat_c, feat_out, dist_out, dist_tot,
-                              *((color, depth) if want_absgrad else ()))
+                              *((color, depth) if want_absgrad else ()), *(hits[1:] if hits_grad else ()))
+        ctx.hits_grad = n_hits if hits_grad else 0
         ctx.scratch_fresh = scratch is not None  # (a second backward over this forward clears a scratch of its own)
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
@@ -833,7 +870,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if dist_out is not None:
             out += (dist_out,)
         if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
-            ctx.mark_non_differentiable(radii, *contrib, *picks)
+            ctx.mark_non_differentiable(radii, *contrib, *(picks[:-3] + picks[-1:] if hits_grad else picks))
             out += contrib + picks
         return out
 
@@ -844,6 +881,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch, feat,
          feat_out, dist_out, dist_tot) = ctx.saved_tensors[:21]
         sink = getattr(ctx, "absgrad_sink", None)
+        n_hits = int(getattr(ctx, "hits_grad", 0) or 0)   # (> 0: the outputs end in index, WEIGHT, REST, count, the saved tensors in weight, rest, count)
+        grad_hw, grad_hr = (_f32c(grad_extra[-3]), _f32c(grad_extra[-2])) if n_hits else (None, None)
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
         grad_feat = grad_extra[int(want_alpha)] if has_feat else None
@@ -893,6 +932,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_dist is not None:   # … and the distortion loss's, the depth value's among them
                 _distortion_backward(lib, st, None, geom, img, binb, ctx.num_rendered, dist_out, dist_tot, _f32c(grad_dist),
                                      scratch, zeroed, stream)
+                zeroed = True
+            if grad_hw is not None or grad_hr is not None:   # … and those of a loss over the hit weights / the rest (csrc/blend_hits_grad.hip)
+                _pixel_hits_backward(lib, st, None, geom, img, binb, ctx.num_rendered, n_hits, *ctx.saved_tensors[-3:], grad_hw,
+                                     grad_hr, scratch, zeroed, stream)
                 zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
@@ -1054,7 +1097,8 @@ class _RasterizeViews(torch.autograd.Function):
                 picks = _pixel_picks(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, (V, H, W), dev, stream)
             n_hits = int(getattr(rs, "return_hits", 0) or 0)
             if n_hits:
-                picks += _pixel_hits(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (V, H, W), dev, stream)
+                hits = _pixel_hits(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (V, H, W), dev, stream)
+                picks += hits
         _tls.last_forward = (geom, P * V) if capacity > 0 else (None, int(fout.num_rendered))
         _tls.last_binning = (int(fout.depth_sort_used), int(fout.max_list_len))
         ctx.raster_settings = rs
@@ -1067,10 +1111,13 @@ class _RasterizeViews(torch.autograd.Function):
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None,
                    means2D is not None)
         want_absgrad = bool(getattr(rs, "absgrad", False)) and not infer and means2D is not None
+        # hits_grad: weight and rest leave as differentiable outputs; the backward replays the lists over what the hit pass wrote
+        hits_grad = bool(n_hits) and bool(getattr(rs, "hits_grad", False)) and not infer
         ctx.absgrad_sink = means2D if want_absgrad else None
         ctx.save_for_backward(means3D_c, sh_c, cp_c, op_c, sc_c, rot_c, cov_c, bg_c, view, proj, cam, radii, geom,
                               img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out, dist_out, dist_tot,
-                              *((color, depth) if want_absgrad else ()))
+                              *((color, depth) if want_absgrad else ()), *(hits[1:] if hits_grad else ()))
+        ctx.hits_grad = n_hits if hits_grad else 0
         ctx.scratch_fresh = scratch is not None
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
@@ -1080,7 +1127,7 @@ class _RasterizeViews(torch.autograd.Function):
         if dist_out is not None:
             out += (dist_out,)
         if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
-            ctx.mark_non_differentiable(radii, *contrib, *picks)
+            ctx.mark_non_differentiable(radii, *contrib, *(picks[:-3] + picks[-1:] if hits_grad else picks))
             out += contrib + picks
         return out
 
@@ -1091,6 +1138,8 @@ class _RasterizeViews(torch.autograd.Function):
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, tf, sc_in,
          fwd_scratch, feat, feat_out, dist_out, dist_tot) = ctx.saved_tensors[:23]
         sink = getattr(ctx, "absgrad_sink", None)
+        n_hits = int(getattr(ctx, "hits_grad", 0) or 0)   # (> 0: the outputs end in index, WEIGHT, REST, count, the saved tensors in weight, rest, count)
+        grad_hw, grad_hr = (_f32c(grad_extra[-3]), _f32c(grad_extra[-2])) if n_hits else (None, None)
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
         grad_alpha = grad_extra[0] if want_alpha else None
         grad_feat = grad_extra[int(want_alpha)] if has_feat else None
@@ -1139,6 +1188,10 @@ class _RasterizeViews(torch.autograd.Function):
             if grad_dist is not None:
                 _distortion_backward(lib, st, vw, geom, img, binb, ctx.num_rendered, dist_out, dist_tot, _f32c(grad_dist),
                                      scratch, zeroed, stream)
+                zeroed = True
+            if grad_hw is not None or grad_hr is not None:   # … and those of a loss over the hit weights / the rest (csrc/blend_hits_grad.hip)
+                _pixel_hits_backward(lib, st, vw, geom, img, binb, ctx.num_rendered, n_hits, *ctx.saved_tensors[-3:], grad_hw,
+                                     grad_hr, scratch, zeroed, stream)
                 zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),

@@ -175,7 +175,7 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,
-                       antialiasing=False, return_alpha=False, *, return_hits=0, return_picks=False,
+                       antialiasing=False, return_alpha=False, *, hits_grad=False, return_hits=0, return_picks=False,
                        return_contributions=False):
     """Everything ``render_cuda`` hands to the rasterizer, batched: a list of
     (GaussianRasterizationSettings, kwargs) per view.  Split out so the golden-vector tests can
@@ -224,7 +224,7 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
             sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}),
             **({"antialiasing": True} if antialiasing else {}), **({"return_alpha": True} if return_alpha else {}),
             **({"return_contributions": True} if return_contributions else {}),
-            **({"return_picks": True} if return_picks else {}), **({"return_hits": return_hits} if return_hits else {}))
+            **({"return_picks": True} if return_picks else {}), **({"return_hits": return_hits} if return_hits else {}), **({"hits_grad": True} if hits_grad else {}))
         kwargs = dict(means3D=gaussian_means[i], shs=shs[i] if use_sh else None,
                       colors_precomp=None if use_sh else shs[i, :, 0, :],
                       opacities=gaussian_opacities[i, ..., None])
@@ -288,7 +288,7 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
                 scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                gaussian_features: Optional[Tensor] = None, *, return_hits: int = 0, return_picks: bool = False,
+                gaussian_features: Optional[Tensor] = None, *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
                 return_contributions: bool = False):
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
@@ -312,12 +312,15 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     planes: per pixel the median depth / index, the dominant weight / index and the contributor count of the same pass.
 
     ``return_hits=K`` (extension; keyword-only, 1 <= K <= 32): a ``PixelHits`` behind even that — ``index`` / ``weight``
-    ``[batch,K,h,w]``, ``rest`` / ``count`` ``[batch,h,w]``: per pixel the first K composited Gaussians of the same pass."""
+    ``[batch,K,h,w]``, ``rest`` / ``count`` ``[batch,h,w]``: per pixel the first K composited Gaussians of the same pass.
+    ``hits_grad=True`` (keyword-only; needs ``return_hits``): its ``weight`` and ``rest`` are differentiable
+    (``GaussianRasterizationSettings.hits_grad``).  The other render functions and ``DecoderSplattingCUDA.forward`` take the
+    same keyword."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing,
                                return_alpha, return_picks=return_picks, return_contributions=return_contributions,
-                               return_hits=return_hits)
+                               return_hits=return_hits, hits_grad=hits_grad)
     outs = _rasterize_views(calls, features=gaussian_features)
     fi, ci = _tail_index(return_contributions, return_picks, return_hits)
     pi = _pick_index(return_hits)
@@ -377,7 +380,7 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
                            gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
                            antialiasing: bool = False, return_alpha: bool = False,
-                           gaussian_features: Optional[Tensor] = None, *, return_hits: int = 0, return_picks: bool = False,
+                           gaussian_features: Optional[Tensor] = None, *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
                            return_contributions: bool = False):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
@@ -397,7 +400,7 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing, return_alpha,
-                               return_picks=return_picks, return_contributions=return_contributions, return_hits=return_hits)
+                               return_picks=return_picks, return_contributions=return_contributions, return_hits=return_hits, hits_grad=hits_grad)
     outs = _rasterize_views(calls, aux=aux, features=gaussian_features)
     fi, ci = _tail_index(return_contributions, return_picks, return_hits)
     pi = _pick_index(return_hits)
@@ -417,7 +420,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
                        sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                       gaussian_features: Optional[Tensor] = None, *, return_hits: int = 0, return_picks: bool = False,
+                       gaussian_features: Optional[Tensor] = None, *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
                        return_contributions: bool = False):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
@@ -503,7 +506,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[0], projmatrix=full[0], sh_degree=degree, campos=campos[0], prefiltered=False,
             list_capacity=list_capacity * n, sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
         out = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
@@ -550,7 +553,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[idx[0]], projmatrix=full[idx[0]], sh_degree=degree, campos=campos[idx[0]],
             prefiltered=False, list_capacity=list_capacity * len(idx), sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         out = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
                               take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
@@ -589,7 +592,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             input_scale=None if scale is None else scale[i:i + 1], sh_channel_major=True, aux_affine=aux_affine,
             tanfov=None if tanfov is None else tanfov[i], sh_max_degree=sh_cap,
             scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
         means = g_means[b]
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
@@ -693,7 +696,7 @@ class DecoderSplattingCUDA(nn.Module):
     def forward(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                 image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None,
                 return_alpha: bool = False, gaussian_features: Optional[Tensor] = None,
-                *, return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False) -> DecoderOutput:
+                *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False) -> DecoderOutput:
         """``scissor=(x0, y0, x1, y1)`` (extension, fused path): render only that pixel window's tiles — the
         deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``.  ``return_alpha=True`` (extension): the output's
         ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it.
@@ -726,7 +729,7 @@ class DecoderSplattingCUDA(nn.Module):
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
                 scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
-                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits)
+                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
@@ -740,7 +743,7 @@ class DecoderSplattingCUDA(nn.Module):
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
                 sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
                 gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                return_picks=want_picks, return_hits=n_hits, **self._ellipsoids(gaussians, v))
+                return_picks=want_picks, return_hits=n_hits, hits_grad=hits_grad, **self._ellipsoids(gaussians, v))
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
@@ -752,7 +755,7 @@ class DecoderSplattingCUDA(nn.Module):
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
                             antialiasing=self.antialiasing, return_alpha=return_alpha,
                             gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                            return_picks=want_picks, return_hits=n_hits, **self._ellipsoids(gaussians, v))
+                            return_picks=want_picks, return_hits=n_hits, hits_grad=hits_grad, **self._ellipsoids(gaussians, v))
         features, contributions, picks, hits = None, None, None, None
         if n_hits:   # (the last element; what is left is the result without it)
             color, hits = (color[:-1] if len(color) > 2 else color[0]), PixelHits(*(unflat(t) for t in color[-1]))

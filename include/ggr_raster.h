@@ -642,8 +642,8 @@ int ggr_means2d_absgrad(const GgrSettings* settings, const GgrViews* views /* NU
  *     out_count  int32   [H,W]    the number of live entries — all of them, not min(count, K)    (no live entry: 0)
  * Ids are Gaussian indices in [0,P) WITHIN THE VIEW'S GAUSSIAN SET (the list id, a row of the [V·P] arrays, minus view·P), as in
  * the pick pass.  Pixels of tiles outside the scissor window, and of frames with num_rendered == 0, get the padding values.  The
- * call writes EVERY element of every requested array: the caller clears nothing.  Forward only: the arrays are not
- * differentiable (a gradient through `weight` would be a backward pass of its own over the lists).  No atomic and no cross-lane
+ * call writes EVERY element of every requested array: the caller clears nothing.  This call is forward only; a loss over
+ * out_weight / out_rest is differentiated by ggr_pixel_hits_backward, below.  No atomic and no cross-lane
  * sum: out_rest is a per-pixel sum in list order, so all four arrays are bit-identical from run to run, across the forms of the
  * depth sort, across reference_rects and between a training and a no_backward forward.
  * Relation to the other outputs: Σ_k out_weight + out_rest == alpha up to the rounding of the two summation orders; out_count
@@ -674,6 +674,55 @@ typedef struct GgrHitPass {
 } GgrHitPass;
 
 int ggr_pixel_hits(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrHitPass* pass, void* stream);
+
+/* ---- the hit pass's backward: a loss over out_weight / out_rest differentiated (ABI 11, additive) -------------------------------
+ * Makes the pixel <-> Gaussian association something geometry can learn from.  For a pixel with LIVE entries i = 0..n-1 in list
+ * order (n = out_count; alpha_i, T_i and w_i = alpha_i*T_i the colour blend's own values), the upstream gradient of entry i is
+ *     g_i = dL_dweight[i]  (i < K)          g_i = dL_drest  (i >= K)
+ * and
+ *     dL/dalpha_i = T_i*g_i - S_i/(1 - alpha_i),     S_i = sum_{j behind i} g_j*w_j.
+ * (The kernel splits a per-pixel constant c off the g -- dL_drest where n > K -- whose part of the sum it takes from the
+ * forward's final transmittance, sum_{j behind i} w_j = T_{i+1} - T_final, and runs the recurrence over the K slots with g - c and
+ * the weights the forward wrote: a loss in which the g nearly agree, alpha = sum weight + rest at the extreme, loses nothing to
+ * cancellation.)
+ * dL/dalpha is chained to the 2D mean, the conic and the opacity (the compensated one under antialiasing) exactly as
+ * ggr_features_backward / ggr_distortion_backward chain theirs: the 0.99 cap passes the gradient straight through; skip,
+ * threshold and stop decisions are constants; the stop entry and skipped entries get nothing.  What the forward PADDED is never
+ * read, in `weight`, `dL_dweight` or `dL_drest`: slots k >= count, and the rest of a pixel with count <= K -- a NaN there
+ * reaches no result.  `rest` itself is not read by this implementation and may be NULL.  A pixel whose gradients are all exactly zero takes no entry.
+ *
+ * Protocol, as ggr_features_backward.  ggr_pixel_hits_backward runs AFTER ggr_pixel_hits over the same forward (same buffers,
+ * num_hits, views and scissor; out_weight and out_count written) and BEFORE that frame's ggr_backward*: it
+ * adds the loss's gradient w.r.t. the 2D mean, conic and opacity into the backward scratch (clearing it first unless
+ * scratch_zeroed = 1), and the caller then passes scratch_zeroed = 1 to ggr_backward*, which carries the sums on to means3D,
+ * covariance / scale / rotation, opacity and the camera.  It may share a scratch with ggr_features_backward and
+ * ggr_distortion_backward, in any order (every one but the first called gets scratch_zeroed = 1).  The forward must be a TRAINING
+ * forward (not no_backward): ggr_backward* needs its state, and this call reads the final transmittance a training forward
+ * leaves in image_buffer; it cannot tell the smaller inference buffers apart and does not check.  `views` NULL: one view; else the GgrViews of the launch set -- only num_views / num_sets are read.  It allocates
+ * nothing, reads nothing back and is hipGraph-capturable.  The sums are accumulated with float atomics: reproducible up to the
+ * order of their additions.  ggr_means2d_absgrad does NOT include these terms.  dL_dweight or dL_drest may be NULL (zeros).
+ * GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, num_hits
+ * outside 1..GGR_MAX_HITS, a nonzero `reserved`, a negative size, dL_dweight and dL_drest both NULL, or a NULL buffer / array the
+ * call needs (geom_buffer, image_buffer, binning_buffer unless num_rendered == 0, weight, count, scratch). */
+typedef struct GgrHitGradPass {
+    int32_t struct_size;            /* sizeof(GgrHitGradPass) */
+    int32_t num_hits;               /* K of the ggr_pixel_hits call, 1..GGR_MAX_HITS */
+    const void* geom_buffer;        /* the forward's */
+    const void* image_buffer;
+    const void* binning_buffer;     /* may be NULL when num_rendered == 0 */
+    int64_t num_rendered;           /* the forward's (−1: sync-free mode) */
+    const float* weight;            /* device [K,H,W] / [V,K,H,W]: GgrHitPass.out_weight as ggr_pixel_hits wrote it */
+    const float* rest;              /* device [H,W] / [V,H,W]: GgrHitPass.out_rest, or NULL (not read) */
+    const int32_t* count;           /* device [H,W] / [V,H,W]: GgrHitPass.out_count */
+    const float* dL_dweight;        /* device, shape of weight, or NULL (zeros) */
+    const float* dL_drest;          /* device, shape of rest, or NULL (zeros); not both NULL */
+    void* scratch;                  /* the ggr_backward_scratch_bytes(_views) buffer this frame's ggr_backward* gets */
+    int32_t scratch_zeroed;         /* 1 = `scratch` is already clear (GgrBackwardIn.scratch_zeroed's meaning) */
+    int32_t reserved;               /* 0 */
+} GgrHitGradPass;
+
+int ggr_pixel_hits_backward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrHitGradPass* pass,
+                            void* stream);
 
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
