@@ -87,6 +87,12 @@ class GgrBackwardExtra(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("dL_dout_alpha", C.c_void_p)]
 
 
+class GgrBackwardExtra2(C.Structure):
+    """GgrBackwardExtra with dL_dtanfov behind it: the `_ext` backward calls take either, struct_size tells which."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("dL_dout_alpha", C.c_void_p),
+                ("dL_dtanfov", C.c_void_p)]
+
+
 def forward_extra(out_alpha=None) -> GgrForwardExtra:
     """The extra planes of ggr_forward_ext / ggr_forward_views_ext (include/ggr_raster.h), struct_size filled in."""
     return GgrForwardExtra(struct_size=C.sizeof(GgrForwardExtra), reserved=0, out_alpha=out_alpha)
@@ -95,6 +101,14 @@ def forward_extra(out_alpha=None) -> GgrForwardExtra:
 def backward_extra(dL_dout_alpha=None) -> GgrBackwardExtra:
     """The extra planes of ggr_backward_ext / ggr_backward_views_ext, struct_size filled in."""
     return GgrBackwardExtra(struct_size=C.sizeof(GgrBackwardExtra), reserved=0, dL_dout_alpha=dL_dout_alpha)
+
+
+def backward_extra2(dL_dout_alpha=None, dL_dtanfov=None):
+    """A GgrBackwardExtra2 (struct_size filled in) as the `extra` argument of ggr_backward_ext / ggr_backward_views_ext:
+    returns (pointer for the call, the struct — keep it alive across the call)."""
+    ex = GgrBackwardExtra2(struct_size=C.sizeof(GgrBackwardExtra2), reserved=0, dL_dout_alpha=dL_dout_alpha,
+                           dL_dtanfov=dL_dtanfov)
+    return C.cast(C.pointer(ex), C.POINTER(GgrBackwardExtra)), ex
 
 
 MAX_FEATURES = 32   # GGR_MAX_FEATURES
@@ -246,6 +260,8 @@ SYMBOLS = [
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),
     ("ggr_camera_setup", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ggr_camera_setup_backward", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ggr_forward_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),
     ("ggr_sort_stats_async", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ("ggr_mark_visible", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

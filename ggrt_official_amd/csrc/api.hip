@@ -104,6 +104,12 @@ int validate_extra(const E* ex, const char* name) {
     return GGR_OK;
 }
 
+// GgrBackwardExtra2.dL_dtanfov of an (already validated) backward extra; a struct_size that ends before the field: absent
+float* extra_dtanfov(const GgrBackwardExtra* ex) {
+    if (!ex || ex->struct_size < (int32_t)sizeof(GgrBackwardExtra2)) return nullptr;
+    return reinterpret_cast<const GgrBackwardExtra2*>(ex)->dL_dtanfov;
+}
+
 int validate(const GgrSettings* st, const GgrForwardIn* in) {
     if (!st || !in) return fail(GGR_E_INVALID, "null settings / inputs");
     if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0)
@@ -851,14 +857,17 @@ int forward_impl(const GgrSettings* st, const ViewSet& vs, const GgrForwardIn* i
 }
 
 int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn* in, GgrBackwardOut* out, void* stream,
-                  const float* dL_dalpha) {
+                  const float* dL_dalpha, float* dL_dtanfov) {
     if (!out) return fail(GGR_E_INVALID, "null gradient output struct");
     const int NV = vs.V;
+    if (dL_dtanfov && (!out->dL_dviewmatrix || !out->dL_dprojmatrix || !out->dL_dcampos))
+        return fail(GGR_E_INVALID, "dL_dtanfov needs the three camera gradient outputs (dL_dviewmatrix, dL_dprojmatrix, dL_dcampos)");
     if (st->num_points == 0) {  // nothing to differentiate; camera gradients are zero
         hipStream_t s0 = (hipStream_t)stream;
         if (out->dL_dviewmatrix) HIP_TRY(hipMemsetAsync(out->dL_dviewmatrix, 0, 64 * (size_t)NV, s0));
         if (out->dL_dprojmatrix) HIP_TRY(hipMemsetAsync(out->dL_dprojmatrix, 0, 64 * (size_t)NV, s0));
         if (out->dL_dcampos) HIP_TRY(hipMemsetAsync(out->dL_dcampos, 0, 12 * (size_t)NV, s0));
+        if (dL_dtanfov) HIP_TRY(hipMemsetAsync(dL_dtanfov, 0, 8 * (size_t)NV, s0));
         return GGR_OK;
     }
     if (!out->dL_dmeans3D || !out->dL_dmeans2D || !out->dL_dopacities || !out->dL_dcov3D)
@@ -902,7 +911,7 @@ int backward_impl(const GgrSettings* st, const ViewSet& vs, const GgrBackwardIn*
                                out->dL_dscales, out->dL_drotations, in->fwd.aux_precomp ? out->dL_daux : nullptr,
                                npose ? sc.pose_acc : nullptr, out->dL_dviewmatrix, out->dL_dprojmatrix,
                                out->dL_dcampos, input_form(st, &in->fwd, vs.sets, out->dL_dshs), in->fwd.cov3D_precomp ? 1 : 0,
-                               in->fwd.opacities, g.counters + GGR_CTR_ANTIALIAS /*the forward's mode*/, s);
+                               in->fwd.opacities, g.counters + GGR_CTR_ANTIALIAS /*the forward's mode*/, s, dL_dtanfov);
     KCHECK(dbg, s, "preprocess_bwd");
     tm.mark(GGR_BWD_PREPROCESS);
     return GGR_OK;
@@ -942,7 +951,7 @@ int ggr_backward_ext(const GgrSettings* st, const GgrBackwardExtra* ex, const Gg
     if (!in) return fail(GGR_E_INVALID, "null inputs");
     rc = validate(st, &in->fwd);
     if (rc) return rc;
-    return backward_impl(st, single_view(st, &in->fwd), in, out, stream, ex ? ex->dL_dout_alpha : nullptr);
+    return backward_impl(st, single_view(st, &in->fwd), in, out, stream, ex ? ex->dL_dout_alpha : nullptr, extra_dtanfov(ex));
 }
 
 int ggr_backward(const GgrSettings* st, const GgrBackwardIn* in, GgrBackwardOut* out, void* stream) {
@@ -983,7 +992,7 @@ int ggr_backward_views_ext(const GgrSettings* st, const GgrBackwardExtra* ex, co
     if (rc) return rc;
     ViewSet vs;
     if ((rc = view_set(st, views, &vs)) != 0) return rc;
-    return backward_impl(st, vs, in, out, stream, ex ? ex->dL_dout_alpha : nullptr);
+    return backward_impl(st, vs, in, out, stream, ex ? ex->dL_dout_alpha : nullptr, extra_dtanfov(ex));
 }
 
 int ggr_backward_views(const GgrSettings* st, const GgrViews* views, const GgrBackwardIn* in, GgrBackwardOut* out,
@@ -1378,6 +1387,20 @@ int ggr_camera_setup(int32_t n, const float* extrinsics, const float* intrinsics
     ggr::launch_camera_setup(n, extrinsics, intrinsics, near, far, scale_invariant, viewmatrix, projmatrix, campos,
                              tanfov, scale, (hipStream_t)stream);
     KCHECK(false, (hipStream_t)stream, "camera_setup");
+    return GGR_OK;
+}
+
+int ggr_camera_setup_backward(int32_t n, const float* extrinsics, const float* intrinsics, const float* near, const float* far,
+                              int32_t scale_invariant, const float* dL_dviewmatrix, const float* dL_dprojmatrix,
+                              const float* dL_dcampos, const float* dL_dtanfov, float* dL_dextrinsics, float* dL_dintrinsics,
+                              void* stream) {
+    g_err[0] = 0;
+    if (n < 0 || (n > 0 && (!extrinsics || !intrinsics || !near || !far || !dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos ||
+                            !dL_dtanfov || !dL_dextrinsics || !dL_dintrinsics)))
+        return fail(GGR_E_INVALID, "bad arguments");
+    ggr::launch_camera_setup_bwd(n, extrinsics, intrinsics, near, far, scale_invariant, dL_dviewmatrix, dL_dprojmatrix,
+                                 dL_dcampos, dL_dtanfov, dL_dextrinsics, dL_dintrinsics, (hipStream_t)stream);
+    KCHECK(false, (hipStream_t)stream, "camera_setup_backward");
     return GGR_OK;
 }
 

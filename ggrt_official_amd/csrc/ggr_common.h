@@ -508,7 +508,8 @@ void launch_preprocess_bwd(int P, int D, int M, const float* means3D, const floa
                            float* dL_dview, float* dL_dproj, float* dL_dcampos, InputForm inf,
                            int cov_is_input /*cov3D is the caller's tensor (in its form), not the stored one*/,
                            const float* opacities /*the forward's [P] (read when anti-aliased)*/,
-                           const uint32_t* mode_word /*the forward's GGR_CTR_ANTIALIAS word (device)*/, hipStream_t s);
+                           const uint32_t* mode_word /*the forward's GGR_CTR_ANTIALIAS word (device)*/, hipStream_t s,
+                           float* dL_dtanfov = nullptr /*[V,2] (needs pose_acc); null: not computed, the kernels without it run*/);
 
 void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,
                          hipStream_t s);
@@ -517,6 +518,10 @@ void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, u
 void launch_camera_setup(int n, const float* extrinsics, const float* intrinsics, const float* near, const float* far,
                          int scale_invariant, float* view, float* full, float* campos, float* tanfov, float* scale,
                          hipStream_t s);
+// … and its backward: dL/dextrinsics [n,4,4], dL/dintrinsics [n,3,3] from the gradients of the four outputs (one launch)
+void launch_camera_setup_bwd(int n, const float* extrinsics, const float* intrinsics, const float* near, const float* far,
+                             int scale_invariant, const float* dL_dview, const float* dL_dfull, const float* dL_dcampos,
+                             const float* dL_dtanfov, float* dL_dextrinsics, float* dL_dintrinsics, hipStream_t s);
 
 // util.hip: float4 streaming copy of `bytes` (multiple of 16) — the measured HBM ceiling bench.py quotes
 void launch_copy_f4(const void* src, void* dst, size_t bytes, int blocks /*0 = default*/, hipStream_t s);

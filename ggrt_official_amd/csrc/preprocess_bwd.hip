@@ -771,11 +771,150 @@ preprocess_bwd_sh_views_kernel(int P, int M, int deg, const float* __restrict__ 
     }
 }
 
+// dL/dtan(fov/2) of every view of a launch set, entries 35 / 36 of the view's pose_acc rows (the rows and the block geometry of
+// preprocess_bwd_kernel<POSE>, behind which it runs; pose_finish_kernel<true> reduces them with the other 35).  tan(fov/2)
+// enters the rasterizer through fx = W/(2·tanfovx), fy = H/(2·tanfovy) in the projection Jacobian J of the 2-D covariance
+// alone: the frustum clamp's limit 1.3·tanfov is a constant (as it is for the clamped t.x / t.y, and as the torch oracle has
+// it), the pixel mean goes through projmatrix, the anti-aliasing factor has no focal length in it.  Per Gaussian
+//   fx·dL/dfx = J00·dL/dJ00 + J02·dL/dJ02   (J00 = fx/tz, J02 = −fx·tx/tz², tx the clamped one),
+// and dL/dtanfovx = −(1/tanfovx)·Σ_g fx·dL/dfx(g).  Culled / radius-0 / excluded Gaussians add nothing.
+// A kernel of its own, not a branch of preprocess_bwd_kernel: with the two sums inside that kernel the compiler pairs its
+// multiplies and adds differently (packed math) and the OTHER gradients change in their last bits (measured: 2e-11 on dL/dmeans3D)
+// — here the kernels that write them are the very ones that run without dL_dtanfov.  It re-reads the blend's gradient record
+// (conic and opacity entries), the mean and the covariance: 80 B per (view, Gaussian), no SH, no LDS beyond the reduction.
+__global__ void __launch_bounds__(256)
+preprocess_bwd_fov_kernel(int P, const float* __restrict__ means3D, const float* __restrict__ cov3D, ViewSet vs, int W, int H,
+                          const int32_t* __restrict__ radii, const float* __restrict__ grad2d, float* __restrict__ pose_acc,
+                          InputForm inf, int cov_is_input, const float* __restrict__ opacities,
+                          const uint32_t* __restrict__ mode_word) {
+    __shared__ float wred[4][2];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool aa = mode_word[0] != 0u;
+    const bool in_range = i < P;
+    {   // Gaussian set blockIdx.y (as in preprocess_bwd_kernel)
+        const int set = (int)blockIdx.y, v0 = set * vs.vps;
+        const size_t in_off = (size_t)set * (size_t)P, st_off = (size_t)v0 * (size_t)P;
+        means3D += 3 * in_off; opacities += in_off;
+        if (cov3D) cov3D += cov_is_input ? (size_t)inf.cov_stride * in_off : 6 * st_off;
+        radii += st_off; grad2d += GGR_G2D_STRIDE * st_off;
+        pose_acc += (size_t)v0 * gridDim.x * 64;
+        vs.view += 16 * v0;
+        if (vs.tanfov) vs.tanfov += 2 * v0;
+        if (vs.input_scale) vs.input_scale += v0;
+    }
+    const size_t il = (size_t)min(i, P - 1);
+    const float m0 = means3D[3 * il], m1 = means3D[3 * il + 1], m2 = means3D[3 * il + 2];
+    float cin_in[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (cov_is_input) {
+        if (inf.cov_stride == 9) {
+            const float* c9 = cov3D + 9 * il;
+            cin_in[0] = c9[0]; cin_in[1] = c9[1]; cin_in[2] = c9[2]; cin_in[3] = c9[4]; cin_in[4] = c9[5]; cin_in[5] = c9[8];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; k++) cin_in[k] = cov3D[6 * il + k];
+        }
+    }
+    const float4* recs = reinterpret_cast<const float4*>(grad2d);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma clang loop unroll(disable)
+    for (int v = 0; v < vs.vps; v++) {
+        const size_t o = (size_t)v * P + il;
+        const float4 r1 = recs[(GGR_G2D_STRIDE / 4) * o + 1];                                        // mean.y, conic xx, xy, yy
+        const float2 r2 = *reinterpret_cast<const float2*>(recs + (GGR_G2D_STRIDE / 4) * o + 2);    // opacity, z
+        const bool live = in_range && radii[o] > 0;
+        const float tanfovx = vs.tanfov ? vs.tanfov[2 * v] : vs.tanfovx;
+        const float tanfovy = vs.tanfov ? vs.tanfov[2 * v + 1] : vs.tanfovy;
+        const float in_s = vs.input_scale ? vs.input_scale[v] : 1.0f;
+        float dfx = 0.f, dfy = 0.f;   // fx·dL/dfx, fy·dL/dfy of this Gaussian
+        if (live) {
+            float V[12];
+#pragma unroll
+            for (int k = 0; k < 12; k++) V[k] = vs.view[16 * v + k + (k / 3)];   // V[3·j + c] = view[4·j + c], j < 4, c < 3
+            const float p0 = in_s * m0, p1 = in_s * m1, p2 = in_s * m2;
+            float cov6[6];
+            const float s2 = in_s * in_s;
+            if (cov_is_input) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) cov6[k] = cin_in[k] * s2;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 6; k++) cov6[k] = cov3D[6 * o + k];
+            }
+            const float dcon0 = r1.y, dcon1 = r1.z, dcon2 = r1.w;
+            const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
+            float t0 = V[0] * p0 + V[3] * p1 + V[6] * p2 + V[9];
+            float t1 = V[1] * p0 + V[4] * p1 + V[7] * p2 + V[10];
+            const float t2 = V[2] * p0 + V[5] * p1 + V[8] * p2 + V[11];
+            const float limx = GGR_FRUSTUM_CLAMP * tanfovx, limy = GGR_FRUSTUM_CLAMP * tanfovy;
+            t0 = fminf(limx, fmaxf(-limx, t0 / t2)) * t2;
+            t1 = fminf(limy, fmaxf(-limy, t1 / t2)) * t2;
+            const float J00 = fx / t2, J02 = -(fx * t0) / (t2 * t2);
+            const float J11 = fy / t2, J12 = -(fy * t1) / (t2 * t2);
+            float A0[3], A1[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                A0[j] = J00 * V[3 * j + 0] + J02 * V[3 * j + 2];
+                A1[j] = J11 * V[3 * j + 1] + J12 * V[3 * j + 2];
+            }
+            const float S[9] = {cov6[0], cov6[1], cov6[2], cov6[1], cov6[3], cov6[4], cov6[2], cov6[4], cov6[5]};
+            float SA0[3], SA1[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                SA0[j] = A0[0] * S[j] + A0[1] * S[3 + j] + A0[2] * S[6 + j];
+                SA1[j] = A1[0] * S[j] + A1[1] * S[3 + j] + A1[2] * S[6 + j];
+            }
+            const float a = SA0[0] * A0[0] + SA0[1] * A0[1] + SA0[2] * A0[2] + GGR_DILATION;
+            const float b = SA0[0] * A1[0] + SA0[1] * A1[1] + SA0[2] * A1[2];
+            const float c = SA1[0] * A1[0] + SA1[1] * A1[1] + SA1[2] * A1[2] + GGR_DILATION;
+            const float denom = a * c - b * b;
+            const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+            float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+            if (denom2inv != 0.f) {   // (as preprocess_bwd_kernel, the anti-aliased opacity's term included)
+                dL_da = denom2inv * (-c * c * dcon0 + 2.f * b * c * dcon1 + (denom - a * c) * dcon2);
+                dL_dc = denom2inv * (-a * a * dcon2 + 2.f * a * b * dcon1 + (denom - a * c) * dcon0);
+                dL_db = denom2inv * 2.f * (b * c * dcon0 - (denom + 2.f * b * b) * dcon1 + a * b * dcon2);
+                if (aa) {
+                    const float g_op = r2.x, w = GGR_DILATION, c00 = a - w, c11 = c - w;
+                    const float ratio = (c00 * c11 - b * b) / denom;
+                    const float sc = sqrtf(fmaxf(GGR_AA_MIN_RATIO, ratio));
+                    if (ratio > GGR_AA_MIN_RATIO) {
+                        const float k = g_op * opacities[il] / (2.f * sc * denom * denom);
+                        dL_da += k * w * (w * c11 + c11 * c11 + b * b);
+                        dL_dc += k * w * (w * c00 + c00 * c00 + b * b);
+                        dL_db += k * (-2.f * w * b * (w + c00 + c11));
+                    }
+                }
+            }
+            float dA0[3], dA1[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                dA0[j] = 2.f * SA0[j] * dL_da + SA1[j] * dL_db;
+                dA1[j] = 2.f * SA1[j] * dL_dc + SA0[j] * dL_db;
+            }
+            const float dJ00 = dA0[0] * V[0] + dA0[1] * V[3] + dA0[2] * V[6];
+            const float dJ02 = dA0[0] * V[2] + dA0[1] * V[5] + dA0[2] * V[8];
+            const float dJ11 = dA1[0] * V[1] + dA1[1] * V[4] + dA1[2] * V[7];
+            const float dJ12 = dA1[0] * V[2] + dA1[1] * V[5] + dA1[2] * V[8];
+            dfx = J00 * dJ00 + J02 * dJ02;
+            dfy = J11 * dJ11 + J12 * dJ12;
+        }
+        const float s0 = wave_sum_lane63(dfx), s1 = wave_sum_lane63(dfy);
+        if (lane == 63) { wred[wave][0] = s0; wred[wave][1] = s1; }
+        __syncthreads();
+        if (threadIdx.x < 2)   // fx = W/(2·tanfovx): ∂fx/∂tanfovx = −fx/tanfovx
+            pose_acc[((size_t)v * gridDim.x + blockIdx.x) * 64 + 35 + threadIdx.x] =
+                -(wred[0][threadIdx.x] + wred[1][threadIdx.x] + wred[2][threadIdx.x] + wred[3][threadIdx.x]) /
+                (threadIdx.x == 0 ? tanfovx : tanfovy);
+        __syncthreads();  // (wred is reused by the next view)
+    }
+}
+
 // dL/d(camera of view v)[k] = Σ_blocks pose_acc[(v·nblocks + b)·64 + k]  (one workgroup per (component, view), fixed
-// order → deterministic)
+// order → deterministic).  FOV: components 35 / 36 go to dL/dtanfov [V,2].
+template <bool FOV>
 __global__ void __launch_bounds__(256)
 pose_finish_kernel(const float* __restrict__ pose_acc, int nblocks, float* __restrict__ dL_dview,
-                   float* __restrict__ dL_dproj, float* __restrict__ dL_dcampos) {
+                   float* __restrict__ dL_dproj, float* __restrict__ dL_dcampos, float* __restrict__ dL_dtanfov) {
     __shared__ float sh[256];
     const int k = blockIdx.x, v = blockIdx.y, tid = threadIdx.x;
     pose_acc += (size_t)v * nblocks * 64;
@@ -797,7 +936,8 @@ pose_finish_kernel(const float* __restrict__ pose_acc, int nblocks, float* __res
     if (tid == 0) {  // straight into the caller's tensors (was: 3 tiny device-to-device copies = 3 more launches)
         if (k < 16) dL_dview[16 * v + k] = sh[0];
         else if (k < 32) dL_dproj[16 * v + k - 16] = sh[0];
-        else dL_dcampos[3 * v + k - 32] = sh[0];
+        else if (!FOV || k < 35) dL_dcampos[3 * v + k - 32] = sh[0];
+        else dL_dtanfov[2 * v + k - 35] = sh[0];
     }
 }
 
@@ -810,7 +950,7 @@ void launch_preprocess_bwd(int P, int D, int M, const float* means3D, const floa
                            float* dL_dcolors_precomp, float* dL_dcov3D, float* dL_dscales,
                            float* dL_drotations, float* dL_daux, float* pose_acc, float* dL_dview, float* dL_dproj,
                            float* dL_dcampos, InputForm inf, int cov_is_input, const float* opacities,
-                           const uint32_t* mode_word, hipStream_t s) {
+                           const uint32_t* mode_word, hipStream_t s, float* dL_dtanfov) {
     if (P <= 0) return;
     const int blocks = (P + 255) / 256;
     const int deg = ggr_sh_degree(D, (!has_colors_precomp && shs) ? M : 25, inf.sh_cap);
@@ -850,11 +990,20 @@ void launch_preprocess_bwd(int P, int D, int M, const float* means3D, const floa
         else { if (pose) GGR_LAUNCH_SHV(16, true); else GGR_LAUNCH_SHV(16, false); }
 #undef GGR_LAUNCH_SHV
     };
-    if (pose_acc) {
+    if (pose_acc && dL_dtanfov) {
         GGR_LAUNCH_PBWD_P(true);
         if (sh_split) launch_sh_views(true);
-        hipLaunchKernelGGL(pose_finish_kernel, dim3(35, vs.V), dim3(256), 0, s, pose_acc, blocks, dL_dview, dL_dproj,
-                           dL_dcampos);
+        // dL/dtanfov: entries 35 / 36 of the same rows, from a kernel of its own — the kernels above are the ones a call without
+        // it launches, so every other gradient is theirs, bit for bit
+        hipLaunchKernelGGL(preprocess_bwd_fov_kernel, dim3(blocks, vs.sets), dim3(256), 0, s, P, means3D, cov3D, vs, W, H, radii,
+                           grad2d, pose_acc, inf, cov_is_input, opacities, mode_word);
+        hipLaunchKernelGGL(pose_finish_kernel<true>, dim3(37, vs.V), dim3(256), 0, s, pose_acc, blocks, dL_dview, dL_dproj,
+                           dL_dcampos, dL_dtanfov);
+    } else if (pose_acc) {
+        GGR_LAUNCH_PBWD_P(true);
+        if (sh_split) launch_sh_views(true);
+        hipLaunchKernelGGL(pose_finish_kernel<false>, dim3(35, vs.V), dim3(256), 0, s, pose_acc, blocks, dL_dview, dL_dproj,
+                           dL_dcampos, (float*)nullptr);
     } else {
         GGR_LAUNCH_PBWD_P(false);
         if (sh_split) launch_sh_views(false);

@@ -58,7 +58,9 @@ class _RasterizationSettingsFields(NamedTuple):
     input_scale: Optional[torch.Tensor] = None  # device scalar s: means·s, cov·s², scales·s (the 1/near renorm)
     sh_channel_major: bool = False              # shs given as [P,3,M] (GGRt's harmonics layout) instead of [P,M,3]
     aux_affine: Optional[tuple] = None          # (a, b): depth output = Σ max(a + b·z/s, 0)·α·T (GGRt's depth pass)
-    tanfov: Optional[torch.Tensor] = None       # device [2]: overrides tanfovx / tanfovy without a read-back (camera_setup)
+    tanfov: Optional[torch.Tensor] = None       # device [2]: overrides tanfovx / tanfovy without a read-back (camera_setup);
+    #                         differentiable — when it requires grad the backward returns dL/dtan(fov/2) (through the focal
+    #                         lengths of the splat footprints; the frustum clamp's limit is a constant).  The host floats are not
     scissor: Optional[tuple] = None  # (x0, y0, x1, y1) pixels, half-open: only the tiles overlapping the window are binned
     #                         and blended (the fine-tune loop's per-cell re-render, finetune_ggrt_stable.py:126-142); inside
     #                         them the outputs equal the full-frame render bit for bit, other tiles come out as background
@@ -735,7 +737,8 @@ def _settings_struct(rs: GaussianRasterizationSettings, P: int, M: int, bg, view
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                viewmatrix, projmatrix, campos, aux, raster_settings, grad_mode=True, features=None):
+                viewmatrix, projmatrix, campos, aux, raster_settings, grad_mode=True, features=None, tanfov=None):
+        # (`tanfov` is raster_settings.tanfov once more: autograd differentiates arguments, not a NamedTuple's fields)
         lib = _lib.load()
         rs = raster_settings
         dev = means3D.device
@@ -889,7 +892,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         grad_dist = grad_extra[int(want_alpha) + int(has_feat)] if has_dist else None   # (behind it: the contributions', picks' and hits' None)
         P, M, H, W = ctx.dims
         dev = means3D.device
-        need_pose = any(ctx.needs_input_grad[8:11])
+        need_fov = len(ctx.needs_input_grad) > 15 and ctx.needs_input_grad[15]   # (settings.tanfov requires grad)
+        need_pose = any(ctx.needs_input_grad[8:11]) or need_fov   # (dL/dtanfov rides the camera gradients' partial sums)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if grad_color is None:
@@ -901,6 +905,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_dist is not None and grad_depth is None:   # ggr_backward carries the depth-value term on with a depth gradient
                 grad_depth = torch.zeros((H, W), dtype=torch.float32, device=dev)
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
+            d_tf = torch.empty((2,), dtype=torch.float32, device=dev) if need_fov else None
             d_means3D = torch.empty((P, 3), dtype=torch.float32, device=dev)
             d_means2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
             d_op = torch.empty((P,), dtype=torch.float32, device=dev)
@@ -953,7 +958,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             if prof is not None:
                 bout.stage_ms = C.cast(prof.bwd, C.c_void_p)
                 prof.bwd_calls += 1
-            _check(lib.ggr_backward_ext(C.byref(st), _byref(bextra), C.byref(bin_), C.byref(bout), stream), "ggr_backward")
+            bex, _keep = _lib.backward_extra2(_ptr(grad_alpha), d_tf.data_ptr()) if need_fov else (_byref(bextra), None)
+            _check(lib.ggr_backward_ext(C.byref(st), bex, C.byref(bin_), C.byref(bout), stream), "ggr_backward")
 
         means_shape, sh_shape, op_shape, aux_shape = ctx.in_shapes
         has_sh, has_cp, has_sc, has_cov = ctx.has
@@ -972,7 +978,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_aux.reshape(aux_shape) if d_aux is not None else None,
             None, None,
             d_feat.reshape(feat_shape) if d_feat is not None else None,
-        )
+            d_tf.reshape(rs.tanfov.shape) if need_fov else None,
+        )[:len(ctx.needs_input_grad)]
 
 
 class _RasterizeViews(torch.autograd.Function):
@@ -1108,6 +1115,7 @@ class _RasterizeViews(torch.autograd.Function):
         shp = lambda t: None if t is None else t.shape
         ctx.in_shapes = (means3D.shape, shp(sh), opacities.shape, shp(aux), campos.shape, shp(colors_precomp),
                          shp(scales), shp(rotations), shp(cov3Ds_precomp))
+        ctx.tanfov_shape = tanfov.shape
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None,
                    means2D is not None)
         want_absgrad = bool(getattr(rs, "absgrad", False)) and not infer and means2D is not None
@@ -1147,7 +1155,8 @@ class _RasterizeViews(torch.autograd.Function):
         P, M, H, W, V, B = ctx.dims
         PT = P * B   # rows of the flat [B·P, …] gradient arrays
         dev = means3D.device
-        need_pose = any(ctx.needs_input_grad[7:10])
+        need_fov = ctx.needs_input_grad[14]   # (the tanfov argument requires grad)
+        need_pose = any(ctx.needs_input_grad[7:10]) or need_fov   # (dL/dtanfov rides the camera gradients' partial sums)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if grad_color is None:
@@ -1169,6 +1178,7 @@ class _RasterizeViews(torch.autograd.Function):
             d_view = e(V, 4, 4) if need_pose else None
             d_proj = e(V, 4, 4) if need_pose else None
             d_cam = e(V, 3) if need_pose else None
+            d_tf = e(V, 2) if need_fov else None
             zeroed = bool(getattr(ctx, "scratch_fresh", False)) and fwd_scratch is not None
             ctx.scratch_fresh = False
             scratch = fwd_scratch if zeroed else torch.empty((lib.ggr_backward_scratch_bytes_views(P, V),),
@@ -1209,8 +1219,9 @@ class _RasterizeViews(torch.autograd.Function):
             if prof is not None:
                 bout.stage_ms = C.cast(prof.bwd, C.c_void_p)
                 prof.bwd_calls += 1
-            _check(lib.ggr_backward_views_ext(C.byref(st), _byref(bextra), C.byref(vw), C.byref(bin_), C.byref(bout),
-                                              stream), "ggr_backward_views")
+            bex, _keep = _lib.backward_extra2(_ptr(grad_alpha), d_tf.data_ptr()) if need_fov else (_byref(bextra), None)
+            _check(lib.ggr_backward_views_ext(C.byref(st), bex, C.byref(vw), C.byref(bin_), C.byref(bout), stream),
+                   "ggr_backward_views")
         means_shape, sh_shape, op_shape, aux_shape, cam_shape, cp_shape, sc_shape, rot_shape, cov_shape = ctx.in_shapes
         has_sh, has_cp, has_sc, has_cov, has_m2d = ctx.has
         return (
@@ -1226,7 +1237,7 @@ class _RasterizeViews(torch.autograd.Function):
             d_cam.reshape(cam_shape) if ctx.needs_input_grad[9] else None,
             d_aux.reshape(aux_shape) if d_aux is not None else None,
             d_means2D if has_m2d else None,
-            None, None, None, None, None,
+            None, None, d_tf.reshape(ctx.tanfov_shape) if need_fov else None, None, None,
             d_feat.reshape(feat_shape) if d_feat is not None else None,
         )
 
@@ -1273,29 +1284,61 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
                                bool(getattr(raster_settings, "return_hits", 0)))
 
 
+class _CameraSetup(torch.autograd.Function):
+    """``ggr_camera_setup`` / ``ggr_camera_setup_backward``: one launch each way, everything stays on the device."""
+
+    @staticmethod
+    def forward(ctx, extrinsics, intrinsics, near, far, scale_invariant):
+        lib = _lib.load()
+        dev = extrinsics.device
+        n = int(extrinsics.shape[0])
+        with torch.cuda.device(dev):
+            e, k = _f32c(extrinsics.detach()), _f32c(intrinsics.detach())
+            nr, fr = _f32c(near.detach()), _f32c(far.detach())
+            view = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
+            full = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
+            campos = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            tanfov = torch.empty((n, 2), dtype=torch.float32, device=dev)
+            scale = torch.empty((n,), dtype=torch.float32, device=dev)
+            _check(lib.ggr_camera_setup(n, e.data_ptr(), k.data_ptr(), nr.data_ptr(), fr.data_ptr(), int(bool(scale_invariant)),
+                                        view.data_ptr(), full.data_ptr(), campos.data_ptr(), tanfov.data_ptr(),
+                                        scale.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "ggr_camera_setup")
+        ctx.save_for_backward(e, k, nr, fr)
+        ctx.scale_invariant = int(bool(scale_invariant))
+        ctx.in_meta = ((extrinsics.shape, extrinsics.dtype), (intrinsics.shape, intrinsics.dtype))
+        ctx.mark_non_differentiable(scale)
+        return view, full, campos, tanfov, scale
+
+    @staticmethod
+    def backward(ctx, g_view, g_full, g_campos, g_tanfov, _g_scale):
+        lib = _lib.load()
+        e, k, nr, fr = ctx.saved_tensors
+        dev, n = e.device, int(e.shape[0])
+        with torch.cuda.device(dev):
+            gv, gf, gc, gt = _f32c(g_view), _f32c(g_full), _f32c(g_campos), _f32c(g_tanfov)
+            d_ext = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
+            d_int = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+            _check(lib.ggr_camera_setup_backward(n, e.data_ptr(), k.data_ptr(), nr.data_ptr(), fr.data_ptr(), ctx.scale_invariant,
+                                                 gv.data_ptr(), gf.data_ptr(), gc.data_ptr(), gt.data_ptr(), d_ext.data_ptr(),
+                                                 d_int.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "ggr_camera_setup_backward")
+        (e_shape, e_dt), (k_shape, k_dt) = ctx.in_meta
+        return (d_ext.reshape(e_shape).to(e_dt) if ctx.needs_input_grad[0] else None,
+                d_int.reshape(k_shape).to(k_dt) if ctx.needs_input_grad[1] else None, None, None, None)
+
+
 def camera_setup(extrinsics: torch.Tensor, intrinsics: torch.Tensor, near: torch.Tensor, far: torch.Tensor,
                  scale_invariant: bool = True):
     """Per-view camera quantities of GGRt's call site (reference ``cuda_splatting.py:18-46,66-73,82-89``) from ONE
     kernel launch, all left on the device: returns ``(viewmatrix [n,4,4], projmatrix [n,4,4], campos [n,3],
     tanfov [n,2], scale [n])`` for ``extrinsics [n,4,4]`` (camera-to-world), normalised ``intrinsics [n,3,3]``,
-    ``near/far [n]``.  No autograd (the reference does not differentiate through its settings either)."""
-    lib = _lib.load()
-    dev = extrinsics.device
-    if dev.type != "cuda":
+    ``near/far [n]``.  Differentiable w.r.t. ``extrinsics`` and ``intrinsics`` (one more launch in the backward,
+    ``ggr_camera_setup_backward``; ``near / far`` get no gradient, ``scale`` carries none): the projection is built from
+    ``intrinsics[0]`` for every view, so row 0 of ``intrinsics.grad`` collects the projection terms of all n views, the other
+    rows only their own tan(fov/2) terms."""
+    if extrinsics.device.type != "cuda":
         raise RuntimeError("camera_setup needs ROCm GPU tensors; there is no CPU path")
-    n = int(extrinsics.shape[0])
-    with torch.no_grad(), torch.cuda.device(dev):
-        e, k = _f32c(extrinsics.detach()), _f32c(intrinsics.detach())
-        nr, fr = _f32c(near.detach()), _f32c(far.detach())
-        view = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
-        full = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
-        campos = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        tanfov = torch.empty((n, 2), dtype=torch.float32, device=dev)
-        scale = torch.empty((n,), dtype=torch.float32, device=dev)
-        _check(lib.ggr_camera_setup(n, e.data_ptr(), k.data_ptr(), nr.data_ptr(), fr.data_ptr(), int(bool(scale_invariant)),
-                                    view.data_ptr(), full.data_ptr(), campos.data_ptr(), tanfov.data_ptr(),
-                                    scale.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "ggr_camera_setup")
-    return view, full, campos, tanfov, scale
+    return _CameraSetup.apply(extrinsics, intrinsics, near, far, scale_invariant)
 
 
 def last_forward_status():
@@ -1341,7 +1384,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     rs = raster_settings
     out = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                     cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
-                                    torch.is_grad_enabled(), _none_if_empty(features_precomp))
+                                    torch.is_grad_enabled(), _none_if_empty(features_precomp), getattr(rs, "tanfov", None))
     return _with_contributions(out, bool(getattr(rs, "return_contributions", False)), bool(getattr(rs, "return_picks", False)),
                                bool(getattr(rs, "return_hits", 0)))
 

@@ -463,8 +463,9 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     sh_cap = resolve_sh_max_degree(sh_max_degree)
     ext_orig = extrinsics
     # the per-view camera quantities: one library kernel, everything (incl. tan(fov/2) and 1/near) stays on the
-    # device — or, for poses that carry gradients / CPU golden tests, the reference's torch formulation
-    on_device = device_camera and extrinsics.is_cuda and not (extrinsics.requires_grad or intrinsics.requires_grad)
+    # device — poses / intrinsics that carry gradients included (camera_setup is differentiable: one more launch in the
+    # backward, and the rasterizer returns dL/dtan(fov/2)) — or, for CPU golden tests, the reference's torch formulation
+    on_device = device_camera and extrinsics.is_cuda
     if on_device:
         from .rasterizer import camera_setup
         view, full, campos, tanfov, scale = camera_setup(extrinsics, intrinsics, near, far, scale_invariant)
@@ -480,11 +481,13 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
         else:
             scale, near_s, far_s = None, near, far
         fov = get_fov(intrinsics)
-        tan_host = (0.5 * fov).tan().detach().cpu().tolist()
+        tan_half = (0.5 * fov).tan()
+        tan_host = tan_half.detach().cpu().tolist()
         proj = get_projection_matrix(near_s, far_s, fov[:, 0], fov[:, 1], intrinsics).transpose(1, 2)
         view = torch.linalg.inv(extrinsics).transpose(1, 2)
         full = view @ proj
-        campos, tanfov = extrinsics[:, :3, 3], None
+        # (on the GPU tan(fov/2) goes on as a tensor, so that this branch too gives intrinsics their whole gradient)
+        campos, tanfov = extrinsics[:, :3, 3], (tan_half.float().contiguous() if extrinsics.is_cuda else None)
     fused_cov = gaussians.covariances is not None
     # ---- every batch element in ONE launch set (GgrViews.num_sets): the reference's `(b v)` flattening with
     # per-batch-element Gaussians (decoder_splatting_cuda.py:40-60) without its per-view loop, its v× repeat, or a

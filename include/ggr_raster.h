@@ -396,6 +396,28 @@ typedef struct GgrBackwardExtra {
     const float* dL_dout_alpha;    /* device [H,W] / [V,H,W] or NULL: no gradient w.r.t. alpha (the default kernels run) */
 } GgrBackwardExtra;
 
+/* GgrBackwardExtra with the gradient w.r.t. tan(fov/2) behind it (ABI 11, additive: GgrBackwardExtra keeps its 16 bytes, no
+ * other struct grows, no signature changes).  ggr_backward_ext / ggr_backward_views_ext take either struct through their
+ * `extra` pointer (cast a GgrBackwardExtra2* to const GgrBackwardExtra*): struct_size tells them which one it is, and a
+ * struct_size that ends before dL_dtanfov means "field absent".
+ *
+ * dL_dtanfov: the gradient of the loss w.r.t. GgrSettings.tanfovx / tanfovy (or tanfov_dev [2]; GgrViews.tanfov [V,2] for a
+ * launch set) — overwritten, no need to pre-zero.  tan(fov/2) enters the rasterizer through the focal lengths
+ * fx = W/(2·tanfovx), fy = H/(2·tanfovy) of the projection Jacobian, i.e. through every splat's 2-D covariance:
+ *     dL/dtanfovx = -(fx/tanfovx) · sum over the Gaussians of dL/dfx
+ * The frustum clamp's limit 1.3·tanfov is a constant here, as it is for the clamped t.x / t.y; the pixel means depend on
+ * projmatrix (dL_dprojmatrix), not on tanfov; the anti-aliasing factor has no focal length in it.  Culled, radius-0 and
+ * non-finite-excluded Gaussians add nothing.  The sums ride the camera gradients' per-block partials and are reduced in a
+ * fixed order (bit-reproducible), so dL_dtanfov needs GgrBackwardOut.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos to be
+ * given: without them the call returns GGR_E_INVALID before anything is enqueued.  Requesting it changes no other gradient
+ * (bit for bit); NULL = not computed, and the backward kernels of a call without it run. */
+typedef struct GgrBackwardExtra2 {
+    int32_t struct_size;           /* sizeof(GgrBackwardExtra2) */
+    int32_t reserved;              /* 0 */
+    const float* dL_dout_alpha;    /* as GgrBackwardExtra's */
+    float* dL_dtanfov;             /* device [2] / [V,2] or NULL: not computed */
+} GgrBackwardExtra2;
+
 /* ggr_forward_opt / ggr_backward with extra planes (GgrForwardExtra / GgrBackwardExtra; NULL = without them).  The backward
  * still needs dL_dout_color: pass zeros for an alpha-only loss. */
 int ggr_forward_ext(const GgrSettings* settings, const GgrForwardOptions* options, const GgrForwardExtra* extra,
@@ -734,6 +756,19 @@ int ggr_camera_setup(int32_t n, const float* extrinsics /*[n,4,4] camera-to-worl
                      const float* far /*[n]*/, int32_t scale_invariant, float* viewmatrix /*[n,4,4]*/,
                      float* projmatrix /*[n,4,4]*/, float* campos /*[n,3]*/, float* tanfov /*[n,2]*/,
                      float* scale /*[n]*/, void* stream);
+
+/* The backward of ggr_camera_setup, one launch: dL/dextrinsics [n,4,4] and dL/dintrinsics [n,3,3] (overwritten) from the
+ * gradients w.r.t. its four differentiable outputs (all four required; `scale` and near / far get no gradient) and the
+ * forward's inputs.  fp64 inside, rounded to fp32 once.
+ *   - the translation column carries the `scale` factor in scale_invariant mode, and campos is that scaled column;
+ *   - the projection is built from intrinsics[0] for EVERY view (GGRt's quirk, kept): the projection terms of all n views sum
+ *     into row 0 of dL/dintrinsics — in a fixed order, bit-reproducible — while tan(fov/2) chains into each view's own row;
+ *   - where the forward's acos clamp acted the fov gradient is 0; a singular extrinsic (the forward wrote NaN) gives NaN. */
+int ggr_camera_setup_backward(int32_t n, const float* extrinsics /*[n,4,4]*/, const float* intrinsics /*[n,3,3]*/,
+                              const float* near /*[n]*/, const float* far /*[n]*/, int32_t scale_invariant,
+                              const float* dL_dviewmatrix /*[n,4,4]*/, const float* dL_dprojmatrix /*[n,4,4]*/,
+                              const float* dL_dcampos /*[n,3]*/, const float* dL_dtanfov /*[n,2]*/,
+                              float* dL_dextrinsics /*[n,4,4]*/, float* dL_dintrinsics /*[n,3,3]*/, void* stream);
 
 /* Sync-free mode: num_rendered and the overflow flag of the forward that filled `geom_buffer` (synchronises).
  * `num_points` is what sized that geom buffer: P for ggr_forward, P·V for ggr_forward_views.
