@@ -12,7 +12,7 @@ default, as upstream), and so do the `return_alpha=` extension (False: the 3-tup
 the rasterizer call (None: the tuple as it was), and the `return_contributions=` and `return_picks=` extensions of the settings
 (False: the tuple as it was; `PixelPicks` and `pick_values` are re-exported for the latter).  Nothing else lives here."""
 from ggrt_official_amd import rasterizer as _r
-from ggrt_official_amd.rasterizer import GaussianRasterizationSettings, PixelPicks, pick_values  # noqa: F401
+from ggrt_official_amd.rasterizer import GaussianRasterizationSettings, PixelPicks, Projection, pick_values  # noqa: F401
 
 
 def _with_call_site_cap(raster_settings):
@@ -35,4 +35,4 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                   _with_call_site_cap(raster_settings), aux_precomp, features_precomp)
 
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "PixelPicks", "pick_values"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "PixelPicks", "pick_values", "Projection"]

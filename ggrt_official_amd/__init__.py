@@ -6,11 +6,11 @@ Scope: the rasterizer (forward + backward) behind a C ABI, the c
 (`render_cuda`, `render_depth_cuda`, `DecoderSplattingCUDA`), one-frame-per-GPU sharding helpers and a
 synthetic-scene generator for the benchmark.  Everything else of GGRt is out of scope.
 """
-from .rasterizer import (Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelHits, PixelPicks, clear_list_hints,
+from .rasterizer import (Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelHits, PixelPicks, Projection, clear_list_hints,
                          composite_hits, last_forward_status, list_hint_stats, pick_values, rasterize_gaussians, rasterize_views,
                          set_list_hint, sort_watch_stats)
 
-__all__ = ["Contributions", "PixelPicks", "pick_values", "PixelHits", "composite_hits", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
+__all__ = ["Contributions", "PixelPicks", "pick_values", "PixelHits", "composite_hits", "Projection", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
            "rasterize_views",
            "last_forward_status", "set_list_hint", "list_hint_stats", "clear_list_hints", "sort_watch_stats"]
 __version__ = "0.1.0"

@@ -176,6 +176,19 @@ def hit_grad_pass(**fields) -> GgrHitGradPass:
     return GgrHitGradPass(struct_size=C.sizeof(GgrHitGradPass), **fields)
 
 
+class GgrProjectionPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p), ("radii", C.c_void_p),
+                ("out_means2d", C.c_void_p), ("out_depth", C.c_void_p), ("out_conic", C.c_void_p), ("out_opacity", C.c_void_p),
+                ("out_color", C.c_void_p), ("out_valid", C.c_void_p), ("dL_dmeans2d", C.c_void_p), ("dL_ddepth", C.c_void_p),
+                ("dL_dconic", C.c_void_p), ("dL_dopacity", C.c_void_p), ("dL_dcolor", C.c_void_p), ("scratch", C.c_void_p),
+                ("scratch_zeroed", C.c_int32), ("reserved2", C.c_int32)]
+
+
+def projection_pass(**fields) -> GgrProjectionPass:
+    """The argument of ggr_projection / ggr_projection_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrProjectionPass(struct_size=C.sizeof(GgrProjectionPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -255,6 +268,8 @@ SYMBOLS = [
     ("ggr_pixel_picks", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrPickPass), C.c_void_p]),
     ("ggr_pixel_hits", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrHitPass), C.c_void_p]),
     ("ggr_pixel_hits_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrHitGradPass), C.c_void_p]),
+    ("ggr_projection", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrProjectionPass), C.c_void_p]),
+    ("ggr_projection_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrProjectionPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

@@ -13,6 +13,7 @@
 #include "blend_hits_grad.h"
 #include "blend_dist.h"
 #include "blend_absgrad.h"
+#include "projection.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1241,6 +1242,75 @@ int ggr_pixel_hits_backward(const GgrSettings* st, const GgrViews* views, const 
     ggr::launch_blend_hits_bwd(W, H, im.ranges, (const uint32_t*)hp->binning_buffer, g.splat, im.final_T, hp->num_hits, hp->weight,
                                hp->count, hp->dL_dweight, hp->dL_drest, sc.grad2d, V, s);
     KCHECK(st->debug != 0, s, "blend_hits_bwd");
+    return GGR_OK;
+}
+
+// ---- the projection pass (projection.hip): the per-(view, Gaussian) projection outputs, and the seeding of their gradients -------
+namespace {
+int projection_pass_check(const GgrSettings* st, const GgrViews* views, const GgrProjectionPass* pp, bool backward, int* V) {
+    if (!st || !pp) return fail(GGR_E_INVALID, "null settings / projection pass");
+    if (pp->struct_size < (int32_t)sizeof(GgrProjectionPass))
+        return fail(GGR_E_INVALID, "GgrProjectionPass.struct_size %d is smaller than the %d bytes of its fields", (int)pp->struct_size,
+                    (int)sizeof(GgrProjectionPass));
+    if (pp->reserved != 0 || pp->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrProjectionPass.reserved must be 0, not %d / %d", (int)pp->reserved, (int)pp->reserved2);
+    if (st->num_points < 0 || st->image_width < 0 || st->image_height < 0) return fail(GGR_E_INVALID, "negative size");
+    if (backward) {
+        if (st->num_points > 0 && !pp->dL_dmeans2d && !pp->dL_ddepth && !pp->dL_dconic && !pp->dL_dopacity && !pp->dL_dcolor)
+            return fail(GGR_E_INVALID, "GgrProjectionPass: all five gradients are NULL");
+        if (!pp->scratch) return fail(GGR_E_INVALID, "GgrProjectionPass.scratch is NULL");
+    } else {
+        if (st->num_points > 0 && !pp->out_means2d && !pp->out_depth && !pp->out_conic && !pp->out_opacity && !pp->out_color && !pp->out_valid)
+            return fail(GGR_E_INVALID, "GgrProjectionPass: all six outputs are NULL");
+        if (!pp->geom_buffer) return fail(GGR_E_INVALID, "GgrProjectionPass: null geom buffer of the forward");
+    }
+    if (st->num_points > 0 && !pp->radii) return fail(GGR_E_INVALID, "GgrProjectionPass.radii is NULL");
+    *V = 1;
+    if (views) {
+        if (views->num_views < 1) return fail(GGR_E_INVALID, "GgrViews: num_views must be >= 1");
+        const int sets = views->num_sets > 1 ? views->num_sets : 1;
+        if (views->num_views % sets != 0) return fail(GGR_E_INVALID, "GgrViews: num_views must be a multiple of num_sets");
+        if ((int64_t)views->num_views * st->num_points >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "num_views x num_points too large");
+        *V = views->num_views;
+    }
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_projection(const GgrSettings* st, const GgrViews* views, const GgrProjectionPass* pp, void* stream) {
+    g_err[0] = 0;
+    int V = 1;
+    const int rc = projection_pass_check(st, views, pp, false, &V);
+    if (rc) return rc;
+    const size_t pairs = (size_t)st->num_points * (size_t)V;
+    if (pairs == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GeomLayout g = ggr_carve_geom((void*)pp->geom_buffer, pairs, ggr_sort_segments((size_t)V), /*with_jac=*/false);
+    ggr::launch_projection_unpack(pairs, g.splat, g.colour, pp->radii, pp->out_means2d, pp->out_depth, pp->out_conic,
+                                  pp->out_opacity, pp->out_color, pp->out_valid, s);
+    KCHECK(st->debug != 0, s, "projection_unpack");
+    return GGR_OK;
+}
+
+int ggr_projection_backward(const GgrSettings* st, const GgrViews* views, const GgrProjectionPass* pp, void* stream) {
+    g_err[0] = 0;
+    int V = 1;
+    const int rc = projection_pass_check(st, views, pp, true, &V);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int P1 = st->num_points;
+    BwdScratch sc = ggr_carve_bwd(pp->scratch, (size_t)P1, (size_t)V);
+    if (P1 == 0) {
+        if (!pp->scratch_zeroed) HIP_TRY(hipMemsetAsync(pp->scratch, 0, sc.bytes, s));
+        return GGR_OK;
+    }
+    // not yet clear: the seeding writes every record whole (its clearing), what lies behind the records — the camera
+    // gradients' partial rows — is cleared here
+    if (!pp->scratch_zeroed)
+        HIP_TRY(hipMemsetAsync(sc.pose_acc, 0, sc.bytes - (size_t)((char*)sc.pose_acc - (char*)pp->scratch), s));
+    ggr::launch_projection_seed((size_t)P1 * (size_t)V, st->image_width, st->image_height, pp->radii, pp->dL_dmeans2d, pp->dL_ddepth,
+                                pp->dL_dconic, pp->dL_dopacity, pp->dL_dcolor, sc.grad2d, pp->scratch_zeroed ? 1 : 0, s);
+    KCHECK(st->debug != 0, s, "projection_seed");
     return GGR_OK;
 }
 

@@ -156,16 +156,26 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
     cross-entropy on ``composite_hits``, a penalty on ``rest``, …) then reaches opacities, means, covariances / scales / rotations
     and the camera through a backward pass of its own over the lists (include/ggr_raster.h GgrHitGradPass); ``index`` and ``count``
     stay non-differentiable.  The values are the same bits.  ``absgrad`` does not include these terms.  False, or under
-    ``torch.no_grad()``: exactly as without it — nothing extra allocated, saved or called."""
+    ``torch.no_grad()``: exactly as without it — nothing extra allocated, saved or called.
+
+    ``return_projection`` (bool, default False; keyword only), kept beside the tuple in the same way: also return, as the VERY LAST
+    output (behind even the hits), a ``Projection(means2d, depth, conic, opacity, color, valid)`` of [P] rows ([V,P] from
+    ``rasterize_views``): where every Gaussian lands on the screen — the 2D mean in pixels, the depth value, the conic, the opacity
+    the pixels see and the colour the blend composites, the geometry buffer's own bits (include/ggr_raster.h GgrProjectionPass), 0
+    where ``valid`` (= ``radii > 0``) is False.  The five float fields are DIFFERENTIABLE: a loss over them reaches means,
+    covariances / scales / rotations, opacities, SH / colours, ``aux`` and the camera; upstream gradients on invalid rows are
+    ignored.  ``means2D.grad`` then includes the ``means2d`` term; ``absgrad`` does not include these terms.  False: nothing
+    extra allocated, saved or called."""
     return_contributions = False   # (instances made by `_make` from the bare items)
     return_picks = False
     return_distortion = False
     absgrad = False
     return_hits = 0
     hits_grad = False
+    return_projection = False
 
     def __new__(cls, *args, return_contributions=False, return_picks=False, return_distortion=False, absgrad=False,
-                return_hits=0, hits_grad=False, **kw):
+                return_hits=0, hits_grad=False, return_projection=False, **kw):
         n = len(_RasterizationSettingsFields._fields)
         if len(args) == n + 2:
             args, return_contributions, return_picks = args[:n], args[n], args[n + 1]
@@ -178,6 +188,7 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         self.absgrad = bool(absgrad)
         self.return_hits = _hits_setting(return_hits)
         self.hits_grad = _hits_grad_setting(hits_grad, self.return_hits)
+        self.return_projection = bool(return_projection)
         return self
 
     def _replace(self, **kw):
@@ -187,6 +198,7 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         absg = kw.pop("absgrad", self.absgrad)
         hits = _hits_setting(kw.pop("return_hits", self.return_hits))
         hgrad = _hits_grad_setting(kw.pop("hits_grad", self.hits_grad), hits)
+        proj = kw.pop("return_projection", self.return_projection)
         new = super()._replace(**kw)
         new.return_contributions = bool(on)
         new.return_picks = bool(picks)
@@ -194,15 +206,17 @@ class GaussianRasterizationSettings(_RasterizationSettingsFields):
         new.absgrad = bool(absg)
         new.return_hits = hits
         new.hits_grad = hgrad
+        new.return_projection = bool(proj)
         return new
 
     def _asdict(self):
         return dict(super()._asdict(), absgrad=self.absgrad, return_distortion=self.return_distortion, return_hits=self.return_hits,
-                    hits_grad=self.hits_grad, return_contributions=self.return_contributions, return_picks=self.return_picks)
+                    hits_grad=self.hits_grad, return_projection=self.return_projection,
+                    return_contributions=self.return_contributions, return_picks=self.return_picks)
 
     def __repr__(self):
         return (super().__repr__()[:-1] + f", absgrad={self.absgrad!r}, return_distortion={self.return_distortion!r}"
-                f", return_hits={self.return_hits!r}, hits_grad={self.hits_grad!r}, return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
+                f", return_hits={self.return_hits!r}, hits_grad={self.hits_grad!r}, return_projection={self.return_projection!r}, return_contributions={self.return_contributions!r}, return_picks={self.return_picks!r})")
 
 
 class Contributions(NamedTuple):
@@ -251,6 +265,19 @@ class PixelHits(NamedTuple):
     weight: torch.Tensor   # float32 [K,H,W]: its blend weight w = α·T (the colour blend's bits), 0 for k >= count
     rest: torch.Tensor     # float32 [H,W]: Σ w of the composited entries behind the K-th — what the slots leave out of alpha
     count: torch.Tensor    # int32 [H,W]: the number of composited entries (all of them, not min(count, K))
+
+
+class Projection(NamedTuple):
+    """Per-Gaussian projection outputs (``return_projection``): where each Gaussian lands on the screen, as the blend reads it —
+    [P] rows, [V,P] rows from ``rasterize_views`` (the same-Gaussians form and the Gaussian-set form alike).  The float fields
+    are the geometry buffer's own bits on valid rows and exactly 0 on the others; they are differentiable (a loss over them
+    reaches every input the colour, depth or alpha loss reaches); gradients handed in on invalid rows are ignored."""
+    means2d: torch.Tensor   # float32 [P,2]: pixel coordinates, pixel centres at integers: ((ndc + 1)·W − 1)/2
+    depth: torch.Tensor     # float32 [P]: the depth value the depth plane blends: view z, or aux_precomp / its aux_affine form
+    conic: torch.Tensor     # float32 [P,3]: (a, b, c), power = −½(a·dx² + c·dy²) − b·dx·dy: inverse of the dilated 2D covariance
+    opacity: torch.Tensor   # float32 [P]: the opacity the pixels see (compensated under antialiasing)
+    color: torch.Tensor     # float32 [P,3]: the colour the blend composites: SH evaluated and clamped, or colors_precomp
+    valid: torch.Tensor     # bool [P]: radii > 0; never carries a gradient
 
 
 def composite_hits(values: torch.Tensor, hits: PixelHits) -> torch.Tensor:
@@ -417,6 +444,30 @@ def _pixel_hits_backward(lib, st, vw, geom, img, binb, num_rendered, k, weight, 
     _check(lib.ggr_pixel_hits_backward(C.byref(st), _byref(vw), C.byref(hp), stream), "ggr_pixel_hits_backward")
 
 
+def _projection(lib, st, vw, geom, radii, shape, dev, stream):
+    """ggr_projection over the geometry buffer and radii of the forward that has just returned: the six arrays of `shape` ([P] /
+    [V,P]) rows, in `Projection`'s order.  The call writes every element."""
+    f = lambda *tail: torch.empty(shape + tail, dtype=torch.float32, device=dev)
+    m2d, dep, con, opa, col = f(2), f(), f(3), f(), f(3)
+    valid = torch.empty(shape, dtype=torch.bool, device=dev)
+    pp = _lib.projection_pass(reserved=0, geom_buffer=geom.data_ptr(), radii=_ptr(radii), out_means2d=m2d.data_ptr(),
+                              out_depth=dep.data_ptr(), out_conic=con.data_ptr(), out_opacity=opa.data_ptr(),
+                              out_color=col.data_ptr(), out_valid=valid.data_ptr(), reserved2=0)
+    _check(lib.ggr_projection(C.byref(st), _byref(vw), C.byref(pp), stream), "ggr_projection")
+    return m2d, dep, con, opa, col, valid
+
+
+def _projection_backward(lib, st, vw, geom, radii, grads, scratch, zeroed, stream):
+    """ggr_projection_backward: a loss over the projection outputs is seeded into `scratch` ahead of ggr_backward*, which is then
+    told that the scratch is in use (scratch_zeroed = 1) and given a depth gradient (zeros if the loss has none), so that it
+    carries the depth-value term on.  `grads`: the five upstream gradients in `Projection`'s order, None = no gradient (NULL)."""
+    g_m2d, g_dep, g_con, g_opa, g_col = grads
+    pp = _lib.projection_pass(reserved=0, geom_buffer=geom.data_ptr(), radii=_ptr(radii), dL_dmeans2d=_ptr(g_m2d),
+                              dL_ddepth=_ptr(g_dep), dL_dconic=_ptr(g_con), dL_dopacity=_ptr(g_opa), dL_dcolor=_ptr(g_col),
+                              scratch=scratch.data_ptr(), scratch_zeroed=int(zeroed), reserved2=0)
+    _check(lib.ggr_projection_backward(C.byref(st), _byref(vw), C.byref(pp), stream), "ggr_projection_backward")
+
+
 def _distortion_pass(geom, img, binb, num_rendered, plane, totals, **more):
     return _lib.distortion_pass(reserved=0, geom_buffer=geom.data_ptr(), image_buffer=img.data_ptr(), binning_buffer=_ptr(binb),
                                 num_rendered=int(num_rendered), out_distortion=plane.data_ptr(), totals=_ptr(totals), **more)
@@ -458,13 +509,15 @@ def _means2d_absgrad(lib, st, vw, geom, img, binb, num_rendered, color, depth, g
     sink.absgrad_signed = signed
 
 
-def _with_contributions(out, on: bool, picks: bool = False, hits: bool = False):
+def _with_contributions(out, on: bool, picks: bool = False, hits: bool = False, projection: bool = False):
     """The public tuple: the three trailing arrays of a `return_contributions` call as ONE `Contributions` element — the five
-    planes of a `return_picks` call, behind them, as ONE `PixelPicks` element — and the four arrays of a `return_hits` call,
-    behind those, as ONE `PixelHits` element, last."""
+    planes of a `return_picks` call, behind them, as ONE `PixelPicks` element — the four arrays of a `return_hits` call,
+    behind those, as ONE `PixelHits` element — and the six arrays of a `return_projection` call as ONE `Projection`, last."""
     tail = ()
+    if projection:
+        out, tail = out[:-6], (Projection(*out[-6:]),)
     if hits:
-        out, tail = out[:-4], (PixelHits(*out[-4:]),)
+        out, tail = out[:-4], (PixelHits(*out[-4:]),) + tail
     if picks:
         out, tail = out[:-5], (PixelPicks(*out[-5:]),) + tail
     if on:
@@ -843,6 +896,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             if n_hits:   # per-pixel hit lists over the same lists (csrc/blend_hits.hip); they ride behind the picks
                 hits = _pixel_hits(lib, st, None, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (H, W), dev, stream)
                 picks += hits
+            proj_out = ()
+            if bool(getattr(rs, "return_projection", False)):   # the per-Gaussian projection outputs (csrc/projection.hip)
+                proj_out = _projection(lib, st, None, geom, radii, (P,), dev, stream)
 
         # exact mode: count known, nothing to keep.  Sync-free mode: count + flags live in the geometry buffer on the
         # device, so that (≈100 MB at P = 1 M) buffer stays referenced until this thread's next forward
@@ -864,6 +920,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                               img, holder.get("bin"), aux_c, scratch, feat_c, feat_out, dist_out, dist_tot,
                               *((color, depth) if want_absgrad else ()), *(hits[1:] if hits_grad else ()))
         ctx.hits_grad = n_hits if hits_grad else 0
+        ctx.projection = bool(proj_out)   # (the outputs then end in the six projection arrays; radii is saved as it is)
         ctx.scratch_fresh = scratch is not None  # (a second backward over this forward clears a scratch of its own)
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
@@ -875,6 +932,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
             ctx.mark_non_differentiable(radii, *contrib, *(picks[:-3] + picks[-1:] if hits_grad else picks))
             out += contrib + picks
+        if proj_out:   # (the five float arrays are differentiable outputs, `valid` is not)
+            ctx.mark_non_differentiable(radii, *contrib, *(picks[:-3] + picks[-1:] if hits_grad else picks), proj_out[-1])
+            out += proj_out
         return out
 
     @staticmethod
@@ -884,6 +944,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, fwd_scratch, feat,
          feat_out, dist_out, dist_tot) = ctx.saved_tensors[:21]
         sink = getattr(ctx, "absgrad_sink", None)
+        grad_proj = None
+        if getattr(ctx, "projection", False):   # the outputs end in the six projection arrays: their gradients come off first
+            grad_proj, grad_extra = tuple(_f32c(g) for g in grad_extra[-6:-1]), grad_extra[:-6]
+            if all(g is None for g in grad_proj):
+                grad_proj = None
         n_hits = int(getattr(ctx, "hits_grad", 0) or 0)   # (> 0: the outputs end in index, WEIGHT, REST, count, the saved tensors in weight, rest, count)
         grad_hw, grad_hr = (_f32c(grad_extra[-3]), _f32c(grad_extra[-2])) if n_hits else (None, None)
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
@@ -902,8 +967,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_depth = _f32c(grad_depth)
             grad_alpha = _f32c(grad_alpha)   # (None: the default backward kernels)
             absgrad_grads = (grad_color, grad_depth, grad_alpha)   # (what this backward was handed, before anything is added)
-            if grad_dist is not None and grad_depth is None:   # ggr_backward carries the depth-value term on with a depth gradient
-                grad_depth = torch.zeros((H, W), dtype=torch.float32, device=dev)
+            if (grad_dist is not None or (grad_proj is not None and grad_proj[1] is not None)) and grad_depth is None:
+                grad_depth = torch.zeros((H, W), dtype=torch.float32, device=dev)   # ggr_backward carries the depth-value term on with a depth gradient
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
             d_tf = torch.empty((2,), dtype=torch.float32, device=dev) if need_fov else None
             d_means3D = torch.empty((P, 3), dtype=torch.float32, device=dev)
@@ -941,6 +1006,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_hw is not None or grad_hr is not None:   # … and those of a loss over the hit weights / the rest (csrc/blend_hits_grad.hip)
                 _pixel_hits_backward(lib, st, None, geom, img, binb, ctx.num_rendered, n_hits, *ctx.saved_tensors[-3:], grad_hw,
                                      grad_hr, scratch, zeroed, stream)
+                zeroed = True
+            if grad_proj is not None:   # … and those of a loss over the projection outputs (csrc/projection.hip)
+                _projection_backward(lib, st, None, geom, radii, grad_proj, scratch, zeroed, stream)
                 zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
@@ -1106,6 +1174,9 @@ class _RasterizeViews(torch.autograd.Function):
             if n_hits:
                 hits = _pixel_hits(lib, st, vw, geom, img, holder.get("bin"), fout.num_rendered, n_hits, (V, H, W), dev, stream)
                 picks += hits
+            proj_out = ()
+            if bool(getattr(rs, "return_projection", False)):
+                proj_out = _projection(lib, st, vw, geom, radii, (V, P), dev, stream)
         _tls.last_forward = (geom, P * V) if capacity > 0 else (None, int(fout.num_rendered))
         _tls.last_binning = (int(fout.depth_sort_used), int(fout.max_list_len))
         ctx.raster_settings = rs
@@ -1126,6 +1197,7 @@ class _RasterizeViews(torch.autograd.Function):
                               img, holder.get("bin"), aux_c, tf_c, sc_in, scratch, feat_c, feat_out, dist_out, dist_tot,
                               *((color, depth) if want_absgrad else ()), *(hits[1:] if hits_grad else ()))
         ctx.hits_grad = n_hits if hits_grad else 0
+        ctx.projection = bool(proj_out)   # (the outputs then end in the six projection arrays; radii is saved as it is)
         ctx.scratch_fresh = scratch is not None
         ctx.mark_non_differentiable(radii)
         ctx.outs = (want_alpha, feat_c is not None, None if features is None else features.shape, dist_out is not None)
@@ -1137,6 +1209,9 @@ class _RasterizeViews(torch.autograd.Function):
         if want_contrib or picks:   # (plain arrays behind everything differentiable; the callers below wrap them)
             ctx.mark_non_differentiable(radii, *contrib, *(picks[:-3] + picks[-1:] if hits_grad else picks))
             out += contrib + picks
+        if proj_out:   # (the five float arrays are differentiable outputs, `valid` is not)
+            ctx.mark_non_differentiable(radii, *contrib, *(picks[:-3] + picks[-1:] if hits_grad else picks), proj_out[-1])
+            out += proj_out
         return out
 
     @staticmethod
@@ -1146,6 +1221,11 @@ class _RasterizeViews(torch.autograd.Function):
         (means3D, sh, cp, op, sc, rot, cov, bg, view, proj, cam, radii, geom, img, binb, aux, tf, sc_in,
          fwd_scratch, feat, feat_out, dist_out, dist_tot) = ctx.saved_tensors[:23]
         sink = getattr(ctx, "absgrad_sink", None)
+        grad_proj = None
+        if getattr(ctx, "projection", False):   # the outputs end in the six projection arrays: their gradients come off first
+            grad_proj, grad_extra = tuple(_f32c(g) for g in grad_extra[-6:-1]), grad_extra[:-6]
+            if all(g is None for g in grad_proj):
+                grad_proj = None
         n_hits = int(getattr(ctx, "hits_grad", 0) or 0)   # (> 0: the outputs end in index, WEIGHT, REST, count, the saved tensors in weight, rest, count)
         grad_hw, grad_hr = (_f32c(grad_extra[-3]), _f32c(grad_extra[-2])) if n_hits else (None, None)
         want_alpha, has_feat, feat_shape, has_dist = ctx.outs
@@ -1163,8 +1243,8 @@ class _RasterizeViews(torch.autograd.Function):
                 grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
             grad_color, grad_depth, grad_alpha = _f32c(grad_color), _f32c(grad_depth), _f32c(grad_alpha)
             absgrad_grads = (grad_color, grad_depth, grad_alpha)   # (what this backward was handed, before anything is added)
-            if grad_dist is not None and grad_depth is None:   # ggr_backward_views carries the depth-value term on with a depth gradient
-                grad_depth = torch.zeros((V, H, W), dtype=torch.float32, device=dev)
+            if (grad_dist is not None or (grad_proj is not None and grad_proj[1] is not None)) and grad_depth is None:
+                grad_depth = torch.zeros((V, H, W), dtype=torch.float32, device=dev)   # ggr_backward_views carries the depth-value term on with a depth gradient
             bextra = None if grad_alpha is None else _lib.backward_extra(grad_alpha.data_ptr())
             form, cov_full, sh_cm = ctx.form
             e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -1202,6 +1282,9 @@ class _RasterizeViews(torch.autograd.Function):
             if grad_hw is not None or grad_hr is not None:   # … and those of a loss over the hit weights / the rest (csrc/blend_hits_grad.hip)
                 _pixel_hits_backward(lib, st, vw, geom, img, binb, ctx.num_rendered, n_hits, *ctx.saved_tensors[-3:], grad_hw,
                                      grad_hr, scratch, zeroed, stream)
+                zeroed = True
+            if grad_proj is not None:
+                _projection_backward(lib, st, vw, geom, radii, grad_proj, scratch, zeroed, stream)
                 zeroed = True
             bin_ = _lib.GgrBackwardIn(
                 fwd=_lib.GgrForwardIn(means3D=_ptr(means3D), shs=_ptr(sh), colors_precomp=_ptr(cp), opacities=_ptr(op),
@@ -1281,7 +1364,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, campos, bg, 
                                 input_scale, torch.is_grad_enabled(), _none_if_empty(features_precomp))
     return _with_contributions(out, bool(getattr(raster_settings, "return_contributions", False)),
                                bool(getattr(raster_settings, "return_picks", False)),
-                               bool(getattr(raster_settings, "return_hits", 0)))
+                               bool(getattr(raster_settings, "return_hits", 0)),
+                               bool(getattr(raster_settings, "return_projection", False)))
 
 
 class _CameraSetup(torch.autograd.Function):
@@ -1386,7 +1470,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                     cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos, aux_precomp, rs,
                                     torch.is_grad_enabled(), _none_if_empty(features_precomp), getattr(rs, "tanfov", None))
     return _with_contributions(out, bool(getattr(rs, "return_contributions", False)), bool(getattr(rs, "return_picks", False)),
-                               bool(getattr(rs, "return_hits", 0)))
+                               bool(getattr(rs, "return_hits", 0)), bool(getattr(rs, "return_projection", False)))
 
 
 class GaussianRasterizer(nn.Module):

@@ -35,7 +35,7 @@ from typing import Literal, Optional
 import torch
 from torch import Tensor, nn
 
-from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelHits, PixelPicks
+from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelHits, PixelPicks, Projection
 
 DepthRenderingMode = Literal["depth", "disparity", "relative_disparity", "log"]
 
@@ -88,6 +88,7 @@ class DecoderOutput:
     contributions: Optional[Contributions] = None  # [b, v, g] tensors: Σ w, max w, pixel count (…, return_contributions=True)
     picks: Optional[PixelPicks] = None  # [b, v, h, w] planes: median depth / index, dominant weight / index, count (…, return_picks=True)
     hits: Optional[PixelHits] = None  # index / weight [b, v, K, h, w], rest / count [b, v, h, w]: the first K composited Gaussians (…, return_hits=K)
+    projection: Optional[Projection] = None  # [b, v, g, …] rows: 2D mean, depth value, conic, opacity, colour, valid (…, return_projection=True)
 
 
 def get_fov(intrinsics: Tensor) -> Tensor:
@@ -175,8 +176,8 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,
-                       antialiasing=False, return_alpha=False, *, hits_grad=False, return_hits=0, return_picks=False,
-                       return_contributions=False):
+                       antialiasing=False, return_alpha=False, *, return_projection=False, hits_grad=False, return_hits=0,
+                       return_picks=False, return_contributions=False):
     """Everything ``render_cuda`` hands to the rasterizer, batched: a list of
     (GaussianRasterizationSettings, kwargs) per view.  Split out so the golden-vector tests can
     compare it with what the reference's call site produces.
@@ -224,7 +225,8 @@ def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, backgroun
             sh_max_degree=resolve_sh_max_degree(sh_max_degree), **({} if scissor is None else {"scissor": tuple(scissor)}),
             **({"antialiasing": True} if antialiasing else {}), **({"return_alpha": True} if return_alpha else {}),
             **({"return_contributions": True} if return_contributions else {}),
-            **({"return_picks": True} if return_picks else {}), **({"return_hits": return_hits} if return_hits else {}), **({"hits_grad": True} if hits_grad else {}))
+            **({"return_picks": True} if return_picks else {}), **({"return_hits": return_hits} if return_hits else {}), **({"hits_grad": True} if hits_grad else {}),
+            **({"return_projection": True} if return_projection else {}))
         kwargs = dict(means3D=gaussian_means[i], shs=shs[i] if use_sh else None,
                       colors_precomp=None if use_sh else shs[i, :, 0, :],
                       opacities=gaussian_opacities[i, ..., None])
@@ -265,6 +267,17 @@ def _stack_hits(hs) -> PixelHits:
     return PixelHits(*(torch.stack([getattr(p, f) for p in hs]) for f in PixelHits._fields))
 
 
+def _stack_projections(ps) -> Projection:
+    """Per-call `Projection` → one with a leading axis over the calls"""
+    return Projection(*(torch.stack([getattr(p, f) for p in ps]) for f in Projection._fields))
+
+
+def _split_projection(out, want: bool):
+    """(a rasterizer call's tuple without its `Projection`, the `Projection` or None): with `return_projection` it is the call's
+    very last element, and everything in front of it sits where it sits without the setting"""
+    return (out[:-1], out[-1]) if want else (out, None)
+
+
 def _tail_index(want_contrib: bool, want_picks: bool, want_hits: bool = False):
     """Where a rasterizer call's tuple has (the rendered features, the Contributions): the hits, when on, are its last
     element, the picks, when on, stand in front of them (`_pick_index`), the contributions in front of those, the features in
@@ -288,8 +301,8 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 gaussian_opacities: Tensor, scale_invariant: bool = True, use_sh: bool = True,
                 gaussian_scales: Optional[Tensor] = None, gaussian_rotations: Optional[Tensor] = None,
                 scissor=None, sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                gaussian_features: Optional[Tensor] = None, *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
-                return_contributions: bool = False):
+                gaussian_features: Optional[Tensor] = None, *, return_projection: bool = False, hits_grad: bool = False,
+                return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False):
     """[batch] views → [batch,3,h,w] (reference ``cuda_splatting.py:49-128``).  With
     ``gaussian_covariances=None`` the ellipsoids come as scales + world quaternions (§8f-4).
 
@@ -315,13 +328,19 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     ``[batch,K,h,w]``, ``rest`` / ``count`` ``[batch,h,w]``: per pixel the first K composited Gaussians of the same pass.
     ``hits_grad=True`` (keyword-only; needs ``return_hits``): its ``weight`` and ``rest`` are differentiable
     (``GaussianRasterizationSettings.hits_grad``).  The other render functions and ``DecoderSplattingCUDA.forward`` take the
-    same keyword."""
+    same keyword.
+
+    ``return_projection=True`` (extension; keyword-only): a ``Projection`` of ``[batch,g,…]`` rows behind everything else — per
+    view and Gaussian the 2D mean, depth value, conic, opacity, colour and ``valid``, differentiable
+    (``GaussianRasterizationSettings.return_projection``).  The other render functions and ``DecoderSplattingCUDA.forward``
+    take the same keyword (``DecoderOutput.projection``: ``[b,v,g,…]``)."""
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, scissor, sh_max_degree, antialiasing,
                                return_alpha, return_picks=return_picks, return_contributions=return_contributions,
-                               return_hits=return_hits, hits_grad=hits_grad)
+                               return_hits=return_hits, hits_grad=hits_grad, return_projection=return_projection)
     outs = _rasterize_views(calls, features=gaussian_features)
+    outs, projs = zip(*(_split_projection(o, return_projection) for o in outs)) if outs else ((), ())
     fi, ci = _tail_index(return_contributions, return_picks, return_hits)
     pi = _pick_index(return_hits)
     res = (torch.stack([o[0] for o in outs]),)
@@ -335,6 +354,8 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
         res += (_stack_picks([o[pi] for o in outs]),)
     if return_hits:
         res += (_stack_hits([o[-1] for o in outs]),)
+    if return_projection:
+        res += (_stack_projections(projs),)
     return res if len(res) > 1 else res[0]
 
 
@@ -380,8 +401,8 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
                            use_sh: bool = True, gaussian_scales: Optional[Tensor] = None,
                            gaussian_rotations: Optional[Tensor] = None, sh_max_degree: Optional[int] = None,
                            antialiasing: bool = False, return_alpha: bool = False,
-                           gaussian_features: Optional[Tensor] = None, *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
-                           return_contributions: bool = False):
+                           gaussian_features: Optional[Tensor] = None, *, return_projection: bool = False, hits_grad: bool = False,
+                           return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False):
     """ONE rasterization per view for what the reference obtains from two:
     ``render_cuda`` (colour, :49-128) + ``render_depth_cuda`` (:227-269).
 
@@ -394,14 +415,18 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
     ``features [b,K,h,w]`` of the same pass as the LAST result; with ``return_contributions=True`` a ``Contributions`` of
     ``[b,g]`` tensors behind everything else — except a ``PixelPicks`` of ``[b,h,w]`` planes, the very last result with
     ``return_picks=True`` (keyword-only; its ``median_depth`` holds the depth pass's per-Gaussian value ``max(0.5 + C0·f(z), 0)``)
-    — and, with ``return_hits=K`` (keyword-only), a ``PixelHits`` (``[b,K,h,w]`` / ``[b,h,w]``) behind even that."""
+    — and, with ``return_hits=K`` (keyword-only), a ``PixelHits`` (``[b,K,h,w]`` / ``[b,h,w]``) behind even that; with
+    ``return_projection=True`` (keyword-only) a ``Projection`` of ``[b,g,…]`` rows last of all (its ``depth`` holds the depth
+    pass's per-Gaussian value)."""
     feat = depth_feature(extrinsics, gaussian_means, near, far, depth_mode)  # unscaled, as the reference
     aux = (0.5 + SH_C0 * feat).clamp(min=0.0)
     calls = boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                                gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant,
                                use_sh, gaussian_scales, gaussian_rotations, None, sh_max_degree, antialiasing, return_alpha,
-                               return_picks=return_picks, return_contributions=return_contributions, return_hits=return_hits, hits_grad=hits_grad)
+                               return_picks=return_picks, return_contributions=return_contributions, return_hits=return_hits, hits_grad=hits_grad,
+                               return_projection=return_projection)
     outs = _rasterize_views(calls, aux=aux, features=gaussian_features)
+    outs, projs = zip(*(_split_projection(o, return_projection) for o in outs)) if outs else ((), ())
     fi, ci = _tail_index(return_contributions, return_picks, return_hits)
     pi = _pick_index(return_hits)
     planes = (0, 2, 3) if return_alpha else (0, 2)
@@ -412,7 +437,9 @@ def render_color_and_depth(extrinsics: Tensor, intrinsics: Tensor, near: Tensor,
         res += (_stack_contributions([o[ci] for o in outs]),)
     if return_picks:
         res += (_stack_picks([o[pi] for o in outs]),)
-    return res + (_stack_hits([o[-1] for o in outs]),) if return_hits else res
+    if return_hits:
+        res += (_stack_hits([o[-1] for o in outs]),)
+    return res + (_stack_projections(projs),) if return_projection else res
 
 
 def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape,
@@ -420,8 +447,8 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                        depth_mode: Optional[DepthRenderingMode] = None, scale_invariant: bool = True,
                        device_camera: bool = True, list_capacity: int = 0, batched: bool = True, scissor=None,
                        sh_max_degree: Optional[int] = None, antialiasing: bool = False, return_alpha: bool = False,
-                       gaussian_features: Optional[Tensor] = None, *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
-                       return_contributions: bool = False):
+                       gaussian_features: Optional[Tensor] = None, *, return_projection: bool = False, hits_grad: bool = False,
+                       return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False):
     """The call site with NO torch operation on a Gaussian-sized tensor (SURVEY.md §8 a2 "where time goes"):
 
     * ``device_camera``: view / projection matrices, camera position, tan(fov/2) and 1/near of all views come
@@ -451,9 +478,12 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     a ``PixelPicks`` of ``[n,h,w]`` planes (per pixel the median depth / index, the dominant weight / index and the contributor
     count of the same launch sets; indices within the view's batch element; not differentiable), the very last result — but for
     ``return_hits=K`` (keyword-only, 1 <= K <= 32), which puts a ``PixelHits`` behind it: ``index`` / ``weight`` ``[n,K,h,w]``,
-    ``rest`` / ``count`` ``[n,h,w]``, per pixel the first K composited Gaussians of the same launch sets (not differentiable)."""
+    ``rest`` / ``count`` ``[n,h,w]``, per pixel the first K composited Gaussians of the same launch sets (not differentiable).
+    ``return_projection=True`` (keyword-only): a ``Projection`` of ``[n,g,…]`` rows (per view and Gaussian of its batch element the
+    2D mean, depth value, conic, opacity, colour and ``valid``; differentiable) last of all."""
     n = extrinsics.shape[0]
     has_feat = gaussian_features is not None
+    want_proj = bool(return_projection)
     want_contrib, want_picks, n_hits = bool(return_contributions), bool(return_picks), int(return_hits)
     fi, ci = _tail_index(want_contrib, want_picks, n_hits)   # where a rasterizer call's tuple has the rendered features / contributions
     pi = _pick_index(n_hits)                                  # … and the picks
@@ -509,15 +539,17 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[0], projmatrix=full[0], sh_degree=degree, campos=campos[0], prefiltered=False,
             list_capacity=list_capacity * n, sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad),
+            return_projection=want_proj)
         kw = dict(cov3D_precomp=gaussians.covariances) if fused_cov else dict(scales=gaussians.scales,
                                                                               rotations=gaussians.rotations)
         out = rasterize_views(gaussians.means, gaussians.opacities, view, full, campos, background_color, tf,
                               settings, shs=gaussians.harmonics, aux_precomp=aux, input_scale=scale,
                               features_precomp=gaussian_features, **kw)
+        out, pj = _split_projection(out, want_proj)
         return _fused_result(out[0], out[2] if depth_mode is not None else None, out[3] if return_alpha else None,
                              return_alpha, out[fi] if has_feat else None, out[ci] if want_contrib else None,
-                                 out[pi] if want_picks else None, out[-1] if n_hits else None)
+                                 out[pi] if want_picks else None, out[-1] if n_hits else None, pj)
     # batch element b of every Gaussian tensor WITHOUT `t[b]`: select's backward zero-fills a full [B,…] tensor
     # and copies the slice in, per view (0.2 ms per view for 1 M × 25 SH coefficients).  One unbind per tensor
     # (backward = one stack) — or a free reshape when there is a single batch element, GGRt's case.
@@ -529,7 +561,7 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
                                   per_batch(gaussians.harmonics), per_batch(gaussians.opacities))
     g_scales, g_rot, g_feat = per_batch(gaussians.scales), per_batch(gaussians.rotations), per_batch(gaussian_features)
     colors, depths, alphas, feats, contribs, picks = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
-    hits = [None] * n
+    hits, projs = [None] * n, [None] * n
     groups = {}
     for i in range(n):
         groups.setdefault(int(view_to_batch[i]), []).append(i)
@@ -556,19 +588,23 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             viewmatrix=view[idx[0]], projmatrix=full[idx[0]], sh_degree=degree, campos=campos[idx[0]],
             prefiltered=False, list_capacity=list_capacity * len(idx), sh_channel_major=True, aux_affine=aux_affine,
             sh_max_degree=sh_cap, scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad),
+            return_projection=want_proj)
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         out = rasterize_views(g_means[b], g_op[b][..., None], take(view), take(full), take(campos),
                               take(background_color), tf, settings, shs=g_sh[b], aux_precomp=aux,
                               input_scale=None if scale is None else take(scale),
                               features_precomp=g_feat[b] if has_feat else None, **kw)
+        out, pj = _split_projection(out, want_proj)
         col, dep = out[0], out[2]
         if len(idx) == n and contiguous:  # every view in this one launch set: hand its outputs on as they are
             return _fused_result(col, dep if depth_mode is not None else None, out[3] if return_alpha else None,
                                  return_alpha, out[fi] if has_feat else None, out[ci] if want_contrib else None,
-                                 out[pi] if want_picks else None, out[-1] if n_hits else None)
+                                 out[pi] if want_picks else None, out[-1] if n_hits else None, pj)
         for k, i in enumerate(idx):
             colors[i], depths[i] = col[k], dep[k]
+            if want_proj:
+                projs[i] = Projection(*(t[k] for t in pj))
             if has_feat:
                 feats[i] = out[fi][k]
             if want_contrib:
@@ -595,13 +631,15 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
             input_scale=None if scale is None else scale[i:i + 1], sh_channel_major=True, aux_affine=aux_affine,
             tanfov=None if tanfov is None else tanfov[i], sh_max_degree=sh_cap,
             scissor=None if scissor is None else tuple(scissor), antialiasing=bool(antialiasing),
-            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
+            return_alpha=bool(return_alpha), return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad),
+            return_projection=want_proj)
         means = g_means[b]
         kw = dict(cov3D_precomp=g_cov[b]) if fused_cov else dict(scales=g_scales[b], rotations=g_rot[b])
         # means2D is only a gradient sink (`cuda_splatting.py:95-99`): its values are never read
         sink = torch.empty_like(means).requires_grad_()
         out = GaussianRasterizer(settings)(means3D=means, means2D=sink, opacities=g_op[b][..., None], shs=g_sh[b],
                                            aux_precomp=aux, features_precomp=g_feat[b] if has_feat else None, **kw)
+        out, projs[i] = _split_projection(out, want_proj)
         colors[i], depths[i] = out[0], out[2]
         if has_feat:
             feats[i] = out[fi]
@@ -619,13 +657,13 @@ def render_views_fused(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far
     return _fused_result(stack(colors), stack(depths) if depth_mode is not None else None,
                          stack(alphas) if return_alpha else None, return_alpha, stack(feats) if has_feat else None,
                          _stack_contributions(contribs) if want_contrib else None, _stack_picks(picks) if want_picks else None,
-                         _stack_hits(hits) if n_hits else None)
+                         _stack_hits(hits) if n_hits else None, _stack_projections(projs) if want_proj else None)
 
 
-def _fused_result(color, depth, alpha, return_alpha, features=None, contributions=None, picks=None, hits=None):
+def _fused_result(color, depth, alpha, return_alpha, features=None, contributions=None, picks=None, hits=None, projection=None):
     """render_views_fused's result: (color, depth) as always, (color, depth, alpha) with return_alpha; the rendered feature
-    channels, when asked for, come behind them, the contributions, when asked for, behind those, then the picks, and the
-    hits last"""
+    channels, when asked for, come behind them, the contributions, when asked for, behind those, then the picks, the hits, and
+    the projection last"""
     res = (color, depth, alpha) if return_alpha else (color, depth)
     if features is not None:
         res += (features,)
@@ -633,7 +671,9 @@ def _fused_result(color, depth, alpha, return_alpha, features=None, contribution
         res += (contributions,)
     if picks is not None:
         res += (picks,)
-    return res if hits is None else res + (hits,)
+    if hits is not None:
+        res += (hits,)
+    return res if projection is None else res + (projection,)
 
 
 def contribution_keep_mask(contributions: Contributions, min_weight_max: Optional[float] = None,
@@ -699,7 +739,8 @@ class DecoderSplattingCUDA(nn.Module):
     def forward(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                 image_shape, depth_mode: Optional[DepthRenderingMode] = None, scissor=None,
                 return_alpha: bool = False, gaussian_features: Optional[Tensor] = None,
-                *, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False, return_contributions: bool = False) -> DecoderOutput:
+                *, return_projection: bool = False, hits_grad: bool = False, return_hits: int = 0, return_picks: bool = False,
+                return_contributions: bool = False) -> DecoderOutput:
         """``scissor=(x0, y0, x1, y1)`` (extension, fused path): render only that pixel window's tiles — the
         deferred-backprop cell of ``finetune_ggrt_stable.py:126-142``.  ``return_alpha=True`` (extension): the output's
         ``alpha`` [b,v,h,w] is the accumulated opacity of the colour pass; colour and depth are as without it.
@@ -712,8 +753,12 @@ class DecoderSplattingCUDA(nn.Module):
         nothing was composited) and the contributor count of the colour pass; not differentiable (``pick_values``).
         ``return_hits=K`` (extension; keyword-only, 1 <= K <= 32): the output's ``hits`` holds ``index`` / ``weight`` [b,v,K,h,w]
         and ``rest`` / ``count`` [b,v,h,w] — per pixel the first K Gaussians the colour pass composited, front to back, with
-        their blend weights; not differentiable (``composite_hits``, per view)."""
+        their blend weights; not differentiable (``composite_hits``, per view).
+        ``return_projection=True`` (extension; keyword-only): the output's ``projection`` holds [b,v,g,…] rows — per view and
+        Gaussian the 2D mean, depth value, conic, opacity, colour and ``valid`` of the colour pass, differentiable."""
         b, v = extrinsics.shape[:2]
+        want_proj = bool(return_projection)
+        unflat_j = lambda pj: None if pj is None else Projection(*(t.reshape(b, v, *t.shape[1:]) for t in pj))
         alpha = None
         has_feat = gaussian_features is not None
         want_contrib, want_picks, n_hits = bool(return_contributions), bool(return_picks), int(return_hits)
@@ -732,13 +777,15 @@ class DecoderSplattingCUDA(nn.Module):
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
                 gaussians, [n // v for n in range(b * v)], depth_mode, list_capacity=self.list_capacity,
                 scissor=scissor, sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
-                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad))
+                gaussian_features=gaussian_features, return_contributions=want_contrib, return_picks=want_picks, return_hits=n_hits, hits_grad=bool(hits_grad),
+                return_projection=want_proj)
+            out, pj = _split_projection(out, want_proj)
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]),
                                  None if depth is None else depth.reshape(b, v, *depth.shape[1:]), alpha,
-                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out), unflat_h(out))
+                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out), unflat_h(out), unflat_j(pj))
         if depth_mode is not None and self.fused_depth:
             out = render_color_and_depth(
                 extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(), image_shape, bg,
@@ -746,20 +793,25 @@ class DecoderSplattingCUDA(nn.Module):
                 self._per_view(gaussians.harmonics, v), self._per_view(gaussians.opacities, v), depth_mode,
                 sh_max_degree=self.sh_max_degree, antialiasing=self.antialiasing, return_alpha=return_alpha,
                 gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                return_picks=want_picks, return_hits=n_hits, hits_grad=hits_grad, **self._ellipsoids(gaussians, v))
+                return_picks=want_picks, return_hits=n_hits, hits_grad=hits_grad, return_projection=want_proj,
+                **self._ellipsoids(gaussians, v))
+            out, pj = _split_projection(out, want_proj)
             color, depth = out[0], out[1]
             if return_alpha:
                 alpha = out[2].reshape(b, v, *out[2].shape[1:])
             return DecoderOutput(color.reshape(b, v, *color.shape[1:]), depth.reshape(b, v, *depth.shape[1:]), alpha,
-                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out), unflat_h(out))
+                                 unflat(out[fi]) if has_feat else None, unflat_c(out), unflat_p(out), unflat_h(out), unflat_j(pj))
         color = render_cuda(extrinsics.flatten(0, 1), intrinsics.flatten(0, 1), near.flatten(), far.flatten(),
                             image_shape, bg, self._per_view(gaussians.means, v),
                             self._opt_per_view(gaussians.covariances, v), self._per_view(gaussians.harmonics, v),
                             self._per_view(gaussians.opacities, v), sh_max_degree=self.sh_max_degree,
                             antialiasing=self.antialiasing, return_alpha=return_alpha,
                             gaussian_features=self._opt_per_view(gaussian_features, v), return_contributions=want_contrib,
-                            return_picks=want_picks, return_hits=n_hits, hits_grad=hits_grad, **self._ellipsoids(gaussians, v))
-        features, contributions, picks, hits = None, None, None, None
+                            return_picks=want_picks, return_hits=n_hits, hits_grad=hits_grad, return_projection=want_proj,
+                            **self._ellipsoids(gaussians, v))
+        features, contributions, picks, hits, pj = None, None, None, None, None
+        if want_proj:   # (the very last element; what is left is the result without it)
+            color, pj = (color[:-1] if len(color) > 2 else color[0]), color[-1]
         if n_hits:   # (the last element; what is left is the result without it)
             color, hits = (color[:-1] if len(color) > 2 else color[0]), PixelHits(*(unflat(t) for t in color[-1]))
         if want_picks:   # (then the picks)
@@ -774,7 +826,7 @@ class DecoderSplattingCUDA(nn.Module):
         color = color.reshape(b, v, *color.shape[1:])
         depth = None if depth_mode is None else self.render_depth(gaussians, extrinsics, intrinsics, near, far,
                                                                   image_shape, depth_mode)
-        return DecoderOutput(color, depth, alpha, features, contributions, picks, hits)
+        return DecoderOutput(color, depth, alpha, features, contributions, picks, hits, unflat_j(pj))
 
     def render_depth(self, gaussians: Gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                      image_shape, mode: DepthRenderingMode = "depth") -> Tensor:

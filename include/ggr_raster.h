@@ -746,6 +746,70 @@ typedef struct GgrHitGradPass {
 int ggr_pixel_hits_backward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrHitGradPass* pass,
                             void* stream);
 
+/* ---- the projection pass: the per-Gaussian projection outputs, differentiable (ABI 11, additive) -----------------------------------
+ * Where every Gaussian lands on the screen.  preprocess leaves, per (view, Gaussian) pair, the quantities the blend reads in the
+ * geometry buffer; ggr_projection copies them out — the SAME BITS, nothing is recomputed — as six arrays of [P] rows ([V,P] rows
+ * for a launch set, pair (v, g) at row v*P + g, for the same-Gaussians form and the num_sets form alike):
+ *     out_means2d [P,2] float32  pixel coordinates as the blend reads them (pixel centres at integers: ((ndc + 1)*W - 1)/2)
+ *     out_depth   [P]   float32  the DEPTH VALUE the depth plane blends (GgrPickPass.out_median_depth's): view z, aux_precomp, or
+ *                                max(a + b*z/s, 0) under aux_affine
+ *     out_conic   [P,3] float32  (a, b, c) with power = -1/2*(a*dx^2 + c*dy^2) - b*dx*dy: the inverse of the dilated 2D covariance
+ *     out_opacity [P]   float32  the opacity the pixels see (the compensated one under antialiasing)
+ *     out_color   [P,3] float32  the colour the blend composites: SH evaluated and clamped, or colors_precomp
+ *     out_valid   [P]   uint8    radii > 0 (1 / 0)
+ * Rows with radii <= 0 (culled, outside the frustum or the scissor window, excluded by the non-finite contract) hold 0 in every
+ * float array, whatever the buffer holds there.  Each output may be NULL (not computed); every element of the others is written:
+ * the caller clears nothing.  The output and gradient arrays are dense and need only their element's alignment (4 bytes for the
+ * float arrays: a [P,2] array may start at any float).  ggr_projection runs AFTER ggr_forward* (any variant, any mode, a no_backward forward as well) on the
+ * same stream, over that forward's geom_buffer and radii; it needs neither the image nor the binning buffer, and num_points == 0
+ * and num_rendered == 0 are valid.  The fields do not depend on the scissor beyond `radii`.
+ *
+ * ggr_projection_backward seeds a loss over those arrays: it adds the caller's gradients w.r.t. the five float arrays (shapes
+ * as above; each may be NULL = no gradient, at least one must not be) into the records of the backward scratch, in the records'
+ * units — the mean's in NDC units (x W/2, H/2), the conic's b halved (the convention ggr_backward* reads) — BEFORE that frame's
+ * ggr_backward*, which is then told scratch_zeroed = 1 and carries the sums on: means2d -> means3D and the camera; conic ->
+ * covariance / scales / rotations, means, camera, tanfov; opacity -> opacities (under antialiasing the covariance side too);
+ * color -> SH / colors_precomp and, through the view direction, means and campos, with the clamp mask applied; depth -> means and
+ * camera, or dL_daux.  ggr_backward* carries the depth term on only when it is given a dL_dout_depth plane: a caller without a
+ * loss on out_depth passes a plane of zeros (and, with aux_precomp, a dL_daux output), as for ggr_distortion_backward.
+ * Gradients on rows with radii <= 0 are NOT READ: a NaN there reaches no result.  scratch_zeroed = 0: the call clears the whole
+ * scratch first (the records by writing them whole); 1: it adds, with plain read-modify-write of floats 0..9 of the records of
+ * rows with radii > 0 — each record belongs to one thread and the call is stream-ordered against the other writers.  It may share
+ * a scratch with ggr_features_backward, ggr_distortion_backward and ggr_pixel_hits_backward, in any order (every one but the first
+ * called gets scratch_zeroed = 1).  GgrBackwardOut.dL_dmeans2D then includes the means2d term (in its own NDC units);
+ * ggr_means2d_absgrad does NOT include these terms.  The forward must be a TRAINING forward (not no_backward): ggr_backward* needs
+ * its state; this call cannot tell and does not check (the convention of ggr_pixel_hits_backward).
+ * `views` NULL: one view; else the GgrViews of the launch set — only num_views / num_sets are read.  Both calls allocate nothing,
+ * read nothing back, do not synchronise and are hipGraph-capturable.  GGR_E_INVALID, before anything is enqueued, for a
+ * struct_size smaller than the struct, a nonzero `reserved`, a negative size, or — unless num_points == 0, where there is nothing
+ * to point at — all six outputs NULL (ggr_projection) / all five gradients NULL (ggr_projection_backward) or a NULL radii; and
+ * always for a NULL buffer the call needs (geom_buffer for ggr_projection, scratch for ggr_projection_backward). */
+typedef struct GgrProjectionPass {
+    int32_t struct_size;            /* sizeof(GgrProjectionPass) */
+    int32_t reserved;               /* 0 */
+    const void* geom_buffer;        /* the forward's (ggr_projection_backward does not read it) */
+    const int32_t* radii;           /* device [P] / [V,P]: the forward's */
+    float* out_means2d;             /* device [P,2] / [V,P,2] or NULL */
+    float* out_depth;               /* device [P]   / [V,P]   or NULL */
+    float* out_conic;               /* device [P,3] / [V,P,3] or NULL */
+    float* out_opacity;             /* device [P]   / [V,P]   or NULL */
+    float* out_color;               /* device [P,3] / [V,P,3] or NULL */
+    uint8_t* out_valid;             /* device [P]   / [V,P]   or NULL */
+    const float* dL_dmeans2d;       /* backward: device, shape of out_means2d, or NULL */
+    const float* dL_ddepth;         /* backward: device, shape of out_depth, or NULL */
+    const float* dL_dconic;         /* backward: device, shape of out_conic, or NULL */
+    const float* dL_dopacity;       /* backward: device, shape of out_opacity, or NULL */
+    const float* dL_dcolor;         /* backward: device, shape of out_color, or NULL */
+    void* scratch;                  /* backward: the ggr_backward_scratch_bytes(_views) buffer this frame's ggr_backward* gets */
+    int32_t scratch_zeroed;         /* backward: 1 = `scratch` is already clear / in use (GgrBackwardIn.scratch_zeroed's meaning) */
+    int32_t reserved2;              /* 0 */
+} GgrProjectionPass;
+
+int ggr_projection(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrProjectionPass* pass,
+                   void* stream);
+int ggr_projection_backward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrProjectionPass* pass,
+                            void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
