@@ -189,6 +189,23 @@ def projection_pass(**fields) -> GgrProjectionPass:
     return GgrProjectionPass(struct_size=C.sizeof(GgrProjectionPass), **fields)
 
 
+class GgrAdapterPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("num_cameras", C.c_int32), ("gaussians_per_camera", C.c_int32),
+                ("samples_per_row", C.c_int32), ("d_sh", C.c_int32), ("scale_min", C.c_float), ("scale_max", C.c_float),
+                ("eps", C.c_float), ("debug", C.c_int32), ("reserved2", C.c_int32), ("reserved3", C.c_int32),
+                ("depth", C.c_void_p), ("coords", C.c_void_p), ("raw", C.c_void_p), ("c2w", C.c_void_p), ("Kinv", C.c_void_p),
+                ("q_cam", C.c_void_p), ("scale_mult", C.c_void_p), ("sh_transform", C.c_void_p), ("sh_mask", C.c_void_p),
+                ("out_means", C.c_void_p), ("out_scales", C.c_void_p), ("out_quats", C.c_void_p), ("out_harmonics", C.c_void_p),
+                ("dL_dmeans", C.c_void_p), ("dL_dscales", C.c_void_p), ("dL_dquats", C.c_void_p), ("dL_dharmonics", C.c_void_p),
+                ("dL_draw", C.c_void_p), ("dL_ddepth", C.c_void_p), ("dL_dcoords", C.c_void_p), ("dL_dc2w", C.c_void_p),
+                ("dL_dKinv", C.c_void_p), ("dL_dq_cam", C.c_void_p), ("dL_dscale_mult", C.c_void_p), ("dL_dsh_transform", C.c_void_p)]
+
+
+def adapter_pass(**fields) -> GgrAdapterPass:
+    """The argument of ggr_adapter_forward / ggr_adapter_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrAdapterPass(struct_size=C.sizeof(GgrAdapterPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -270,6 +287,8 @@ SYMBOLS = [
     ("ggr_pixel_hits_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrHitGradPass), C.c_void_p]),
     ("ggr_projection", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrProjectionPass), C.c_void_p]),
     ("ggr_projection_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrProjectionPass), C.c_void_p]),
+    ("ggr_adapter_forward", C.c_int, [C.POINTER(GgrAdapterPass), C.c_void_p]),
+    ("ggr_adapter_backward", C.c_int, [C.POINTER(GgrAdapterPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

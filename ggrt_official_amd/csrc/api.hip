@@ -14,6 +14,7 @@
 #include "blend_dist.h"
 #include "blend_absgrad.h"
 #include "projection.h"
+#include "adapter.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1311,6 +1312,80 @@ int ggr_projection_backward(const GgrSettings* st, const GgrViews* views, const 
     ggr::launch_projection_seed((size_t)P1 * (size_t)V, st->image_width, st->image_height, pp->radii, pp->dL_dmeans2d, pp->dL_ddepth,
                                 pp->dL_dconic, pp->dL_dopacity, pp->dL_dcolor, sc.grad2d, pp->scratch_zeroed ? 1 : 0, s);
     KCHECK(st->debug != 0, s, "projection_seed");
+    return GGR_OK;
+}
+
+// ---- the Gaussian adapter pass (adapter.hip): GGRt's encoder tail, one forward and one backward launch ----------------------------
+namespace {
+int adapter_pass_check(const GgrAdapterPass* ap, bool backward, ggr::AdapterArgs* a) {
+    if (!ap) return fail(GGR_E_INVALID, "null GgrAdapterPass");
+    if (ap->struct_size < (int32_t)sizeof(GgrAdapterPass))
+        return fail(GGR_E_INVALID, "GgrAdapterPass.struct_size %d is smaller than the %d bytes of its fields", (int)ap->struct_size,
+                    (int)sizeof(GgrAdapterPass));
+    if (ap->reserved != 0 || ap->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrAdapterPass.reserved must be 0, not %d / %d", (int)ap->reserved, (int)ap->reserved2);
+    if (ap->num_cameras < 0 || ap->gaussians_per_camera < 0) return fail(GGR_E_INVALID, "GgrAdapterPass: negative size");
+    const int d = ap->d_sh;
+    if (d != 1 && d != 4 && d != 9 && d != 16 && d != 25) return fail(GGR_E_INVALID, "GgrAdapterPass.d_sh must be 1, 4, 9, 16 or 25, not %d", d);
+    if (ap->samples_per_row < 1 || ap->gaussians_per_camera % ap->samples_per_row != 0)
+        return fail(GGR_E_INVALID, "GgrAdapterPass: gaussians_per_camera %d is no multiple of samples_per_row %d",
+                    (int)ap->gaussians_per_camera, (int)ap->samples_per_row);
+    if (ap->num_cameras > 65535) return fail(GGR_E_LIMIT, "GgrAdapterPass: more than 65535 cameras");
+    if ((int64_t)ap->num_cameras * ap->gaussians_per_camera >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "GgrAdapterPass: num_cameras x gaussians_per_camera too large");
+    const bool any = ap->num_cameras > 0 && ap->gaussians_per_camera > 0;
+    const void* need_fwd[] = {ap->depth, ap->coords, ap->raw, ap->c2w, ap->Kinv, ap->q_cam, ap->scale_mult, ap->sh_transform, ap->sh_mask};
+    const char* name_fwd[] = {"depth", "coords", "raw", "c2w", "Kinv", "q_cam", "scale_mult", "sh_transform", "sh_mask"};
+    for (int i = 0; i < 9; ++i)
+        if (any && !need_fwd[i]) return fail(GGR_E_INVALID, "GgrAdapterPass.%s is NULL", name_fwd[i]);
+    const void* need_out[] = {ap->out_means, ap->out_scales, ap->out_quats, ap->out_harmonics};
+    const char* name_out[] = {"out_means", "out_scales", "out_quats", "out_harmonics"};
+    const void* need_bwd[] = {ap->dL_dmeans, ap->dL_dscales, ap->dL_dquats, ap->dL_dharmonics, ap->dL_draw};
+    const char* name_bwd[] = {"dL_dmeans", "dL_dscales", "dL_dquats", "dL_dharmonics", "dL_draw"};
+    if (any && !backward)
+        for (int i = 0; i < 4; ++i)
+            if (!need_out[i]) return fail(GGR_E_INVALID, "GgrAdapterPass.%s is NULL", name_out[i]);
+    if (any && backward)
+        for (int i = 0; i < 5; ++i)
+            if (!need_bwd[i]) return fail(GGR_E_INVALID, "GgrAdapterPass.%s is NULL", name_bwd[i]);
+    const void* all[] = {ap->depth, ap->coords, ap->raw, ap->c2w, ap->Kinv, ap->q_cam, ap->scale_mult, ap->sh_transform, ap->sh_mask,
+                         ap->out_means, ap->out_scales, ap->out_quats, ap->out_harmonics, ap->dL_dmeans, ap->dL_dscales, ap->dL_dquats,
+                         ap->dL_dharmonics, ap->dL_draw, ap->dL_ddepth, ap->dL_dcoords, ap->dL_dc2w, ap->dL_dKinv, ap->dL_dq_cam,
+                         ap->dL_dscale_mult, ap->dL_dsh_transform};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrAdapterPass: a buffer is misaligned (every array needs a float's 4 bytes)");
+    a->C = ap->num_cameras; a->G = ap->gaussians_per_camera; a->spp = ap->samples_per_row; a->d_sh = d;
+    a->scale_min = ap->scale_min; a->scale_max = ap->scale_max; a->eps = ap->eps;
+    a->depth = ap->depth; a->coords = ap->coords; a->raw = ap->raw; a->c2w = ap->c2w; a->Kinv = ap->Kinv; a->q_cam = ap->q_cam;
+    a->scale_mult = ap->scale_mult; a->sh_transform = ap->sh_transform; a->sh_mask = ap->sh_mask;
+    a->means = ap->out_means; a->scales = ap->out_scales; a->quats = ap->out_quats; a->harmonics = ap->out_harmonics;
+    a->g_means = ap->dL_dmeans; a->g_scales = ap->dL_dscales; a->g_quats = ap->dL_dquats; a->g_harmonics = ap->dL_dharmonics;
+    a->g_raw = ap->dL_draw; a->g_depth = ap->dL_ddepth; a->g_coords = ap->dL_dcoords; a->g_c2w = ap->dL_dc2w; a->g_Kinv = ap->dL_dKinv;
+    a->g_q_cam = ap->dL_dq_cam; a->g_scale_mult = ap->dL_dscale_mult; a->g_sh_transform = ap->dL_dsh_transform;
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_adapter_forward(const GgrAdapterPass* ap, void* stream) {
+    g_err[0] = 0;
+    ggr::AdapterArgs a;
+    const int rc = adapter_pass_check(ap, false, &a);
+    if (rc) return rc;
+    if (a.C == 0 || a.G == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_adapter_forward(a, s);
+    KCHECK(ap->debug != 0, s, "adapter_forward");
+    return GGR_OK;
+}
+
+int ggr_adapter_backward(const GgrAdapterPass* ap, void* stream) {
+    g_err[0] = 0;
+    ggr::AdapterArgs a;
+    const int rc = adapter_pass_check(ap, true, &a);
+    if (rc) return rc;
+    if (a.C == 0 || a.G == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_adapter_backward(a, s);
+    KCHECK(ap->debug != 0, s, "adapter_backward");
     return GGR_OK;
 }
 

@@ -32,9 +32,12 @@ from dataclasses import dataclass
 from math import isqrt
 from typing import Literal, Optional
 
+import ctypes as C
+
 import torch
 from torch import Tensor, nn
 
+from . import _lib
 from .rasterizer import Contributions, GaussianRasterizationSettings, GaussianRasterizer, PixelHits, PixelPicks, Projection
 
 DepthRenderingMode = Literal["depth", "disparity", "relative_disparity", "log"]
@@ -171,6 +174,107 @@ def adapter_scale_rotation(scales: Tensor, rotations_xyzw: Tensor, c2w_rotations
                      cw * y - cx * z + cy * w + cz * x,
                      cw * z + cx * y - cy * x + cz * w], -1)
     return scales.broadcast_to(q.shape[:-1] + (3,)), q
+
+
+def adapter_sh_mask(d_sh: int, device=None) -> Tensor:
+    """The reference adapter's harmonics mask [d_sh]: 1 for the DC term, ``0.1·0.25^degree`` for every higher band
+    (``gaussian_adapter.py:39-46``)."""
+    mask = torch.ones(d_sh, dtype=torch.float32, device=device)
+    for degree in range(1, isqrt(d_sh)):
+        mask[degree ** 2:(degree + 1) ** 2] = 0.1 * 0.25 ** degree
+    return mask
+
+
+class _FusedAdapter(torch.autograd.Function):
+    """ggr_adapter_forward / ggr_adapter_backward (csrc/adapter.hip) behind autograd: the per-Gaussian tensors and the tiny
+    per-camera tensors in, (means, scales, quats wxyz, harmonics) out — one launch each way."""
+
+    @staticmethod
+    def forward(ctx, depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, sh_mask, scale_min, scale_max, eps):
+        dev = depth.device
+        if dev.type != "cuda":
+            raise RuntimeError("fused_gaussian_adapter runs on the GPU only (there is no CPU fallback)")
+        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, sh_mask = map(f, (depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, sh_mask))
+        n_cam, g = depth.shape
+        d_sh = sh_t.shape[-1]
+        rows = raw.shape[1]
+        if rows < 1 or g % rows != 0 or raw.shape != (n_cam, rows, 7 + 3 * d_sh):
+            raise ValueError(f"raw_gaussians {tuple(raw.shape)} does not fit {n_cam} cameras x {g} Gaussians with d_sh = {d_sh}")
+        ctx.dims = (n_cam, g, g // rows, d_sh, float(scale_min), float(scale_max), float(eps))
+        p = n_cam * g
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        means, scales, quats, harmonics = new(p, 3), new(p, 3), new(p, 4), new(p, 3, d_sh)
+        ap = _FusedAdapter._pass(ctx.dims, depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, sh_mask, out_means=means.data_ptr(),
+                                 out_scales=scales.data_ptr(), out_quats=quats.data_ptr(), out_harmonics=harmonics.data_ptr())
+        with torch.cuda.device(dev):
+            rc = _lib.load().ggr_adapter_forward(C.byref(ap), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"ggr_adapter_forward failed (code {rc}): {_lib.last_error()}")
+        ctx.save_for_backward(depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, sh_mask)
+        return means, scales, quats, harmonics
+
+    @staticmethod
+    def _pass(dims, depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, sh_mask, **more):
+        n_cam, g, spp, d_sh, scale_min, scale_max, eps = dims
+        return _lib.adapter_pass(reserved=0, num_cameras=n_cam, gaussians_per_camera=g, samples_per_row=spp, d_sh=d_sh,
+                                 scale_min=scale_min, scale_max=scale_max, eps=eps, debug=0, reserved2=0, reserved3=0,
+                                 depth=depth.data_ptr(), coords=coords.data_ptr(), raw=raw.data_ptr(), c2w=c2w.data_ptr(),
+                                 Kinv=kinv.data_ptr(), q_cam=q_cam.data_ptr(), scale_mult=mult.data_ptr(),
+                                 sh_transform=sh_t.data_ptr(), sh_mask=sh_mask.data_ptr(), **more)
+
+    @staticmethod
+    def backward(ctx, g_means, g_scales, g_quats, g_harm):
+        saved = ctx.saved_tensors
+        depth, coords, raw, c2w, kinv, q_cam, mult, sh_t, _ = saved
+        dev = depth.device
+        f = lambda t: t.to(dtype=torch.float32).contiguous()
+        g_means, g_scales, g_quats, g_harm = map(f, (g_means, g_scales, g_quats, g_harm))
+        need = ctx.needs_input_grad
+        d_raw = torch.empty_like(raw)
+        d_depth = torch.empty_like(depth) if need[0] else None
+        d_coords = torch.empty_like(coords) if need[1] else None
+        # the per-camera sums are added into: zero-initialised here, NULL (skipped by the kernel) where nobody asks
+        d_c2w, d_kinv, d_q, d_mult, d_sh_t = (torch.zeros_like(t) if need[i] else None
+                                              for i, t in ((3, c2w), (4, kinv), (5, q_cam), (6, mult), (7, sh_t)))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        ap = _FusedAdapter._pass(ctx.dims, *saved, dL_dmeans=g_means.data_ptr(), dL_dscales=g_scales.data_ptr(),
+                                 dL_dquats=g_quats.data_ptr(), dL_dharmonics=g_harm.data_ptr(), dL_draw=d_raw.data_ptr(),
+                                 dL_ddepth=ptr(d_depth), dL_dcoords=ptr(d_coords), dL_dc2w=ptr(d_c2w), dL_dKinv=ptr(d_kinv),
+                                 dL_dq_cam=ptr(d_q), dL_dscale_mult=ptr(d_mult), dL_dsh_transform=ptr(d_sh_t))
+        with torch.cuda.device(dev):
+            rc = _lib.load().ggr_adapter_backward(C.byref(ap), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"ggr_adapter_backward failed (code {rc}): {_lib.last_error()}")
+        return (d_depth, d_coords, d_raw if need[2] else None, d_c2w, d_kinv, d_q, d_mult, d_sh_t, None, None, None, None)
+
+
+def fused_gaussian_adapter(extrinsics: Tensor, intrinsics: Tensor, coordinates: Tensor, depths: Tensor, raw_gaussians: Tensor,
+                           image_shape, sh_transform: Tensor, *, scale_min: float, scale_max: float,
+                           sh_mask: Optional[Tensor] = None, eps: float = 1e-8) -> Gaussians:
+    """GGRt's ``GaussianAdapter.forward`` (``encoder/common/gaussian_adapter.py:48-96``) as one HIP launch, and one more for its
+    backward.  C source cameras of G Gaussians each: ``extrinsics`` [C,4,4] camera-to-world, ``intrinsics``
+    [C,3,3] normalised, ``coordinates`` [C,G,2], ``depths`` [C,G], ``raw_gaussians`` [C,G/spp,7+3·d_sh] (scale logits 3,
+    quaternion xyzw 4, harmonics ``(xyz d_sh)``; spp consecutive Gaussians share a row — the reference's broadcast sample axis),
+    ``sh_transform`` [C,d_sh,d_sh]: the caller's Wigner-D matrices of the cameras' rotations, of which the diagonal band blocks are
+    read.  ``sh_mask=None``: the reference's (``adapter_sh_mask``).  Returns ``Gaussians`` with P = C·G rows in the form the
+    boundary takes unchanged: ``covariances=None``, world-space ``scales`` [P,3] and ``rotations`` [P,4] (w,x,y,z) as
+    ``adapter_scale_rotation`` gives them, ``harmonics`` [P,3,d_sh]; ``opacities=None`` (not the adapter's business).
+    The per-camera quantities are derived here in torch with autograd on, so gradients reach ``extrinsics``, ``intrinsics`` and
+    ``sh_transform`` through torch's own backward of those tiny ops; the kernels see no Gaussian-sized torch op."""
+    d_sh = sh_transform.shape[-1]
+    if d_sh not in (1, 4, 9, 16, 25) or sh_transform.shape[-2] != d_sh:
+        raise ValueError("sh_transform must be [C, d_sh, d_sh] with d_sh in {1, 4, 9, 16, 25}")
+    h, w = image_shape
+    dev = depths.device
+    if sh_mask is None:
+        sh_mask = adapter_sh_mask(d_sh, dev)
+    pixel_size = torch.tensor([1.0 / w, 1.0 / h], dtype=intrinsics.dtype, device=intrinsics.device)
+    mult = 0.1 * (torch.linalg.inv(intrinsics[..., :2, :2]) @ pixel_size).sum(-1)     # get_scale_multiplier
+    means, scales, quats, harmonics = _FusedAdapter.apply(
+        depths, coordinates, raw_gaussians, extrinsics[..., :3, :4], torch.linalg.inv(intrinsics),
+        matrix_to_quaternion_wxyz(extrinsics[..., :3, :3]), mult, sh_transform, sh_mask, scale_min, scale_max, eps)
+    return Gaussians(means=means, covariances=None, harmonics=harmonics, opacities=None, scales=scales, rotations=quats)
 
 
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,

@@ -810,6 +810,70 @@ int ggr_projection(const GgrSettings* settings, const GgrViews* views /* NULL = 
 int ggr_projection_backward(const GgrSettings* settings, const GgrViews* views /* NULL = one view */, const GgrProjectionPass* pass,
                             void* stream);
 
+/* ---- the Gaussian adapter pass: GGRt's encoder tail in one forward and one backward launch (ABI 11, additive) ---------------------
+ * What GGRt's GaussianAdapter.forward does with a couple of dozen torch launches, in front of the rasterizer: the network's raw
+ * output plus depth and ray coordinates become the means, scales, world-space quaternions and rotated harmonics that GgrForwardIn
+ * takes (scales + rotations, shs with sh_channel_major = 1).  The Gaussians are grouped by source camera: C cameras of G Gaussians,
+ * row p = c*G + g; `samples_per_row` consecutive Gaussians share one raw row (G % samples_per_row == 0).  With (x, y) = coords[p],
+ * [R | t] = c2w[c] and D_band the band's diagonal block (sizes 1, 3, 5, 7, 9) of sh_transform[c]:
+ *     means[p]  = t + R * normalize(Kinv[c] * (x, y, 1)) * depth[p]
+ *     scales[p] = (scale_min + (scale_max - scale_min) * sigmoid(raw[0:3])) * depth[p] * scale_mult[c]
+ *     quats[p]  = q_cam[c] (x) (q / (|q| + eps)),  q = raw[3:7] as (x, y, z, w); the result is (w, x, y, z)
+ *     harmonics[p][ch][band] = D_band * (sh_mask[band] .* raw[7 + ch*d_sh + band])        -- [P, 3, d_sh]: sh_channel_major
+ * Only the diagonal blocks of sh_transform are read (the caller's Wigner-D matrices: nothing is computed from the rotation here).
+ * Opacities are not the adapter's business.  ggr_adapter_forward writes every element of the four outputs.
+ * ggr_adapter_backward takes the gradients w.r.t. the four outputs (all required) and the forward's inputs, and writes every
+ * element of dL_draw (summed over a row's samples in registers: no atomics), dL_ddepth and dL_dcoords (each may be NULL: not
+ * computed); the five per-camera gradients are ADDED, one float atomic per workgroup and element after a reduction on chip, into
+ * buffers the caller has ZERO-INITIALISED — each may be NULL and is then skipped (dL_dsh_transform, the expensive one, selects
+ * another kernel); dL_dsh_transform receives the diagonal blocks only.  Their low bits depend on the order of the atomics.
+ * All arrays are dense float32 on the device and need a float's alignment (4 bytes).  Both calls allocate nothing, read nothing
+ * back, do not synchronise (unless `debug`) and are hipGraph-capturable; num_cameras == 0 or gaussians_per_camera == 0 is valid
+ * and enqueues nothing.  GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero
+ * `reserved`, a negative size, d_sh outside {1, 4, 9, 16, 25}, samples_per_row < 1 or not dividing gaussians_per_camera, a
+ * misaligned buffer, or (unless there are no Gaussians) a NULL required pointer; GGR_E_LIMIT for more than 65535 cameras or
+ * 2^31 - 1 Gaussians. */
+typedef struct GgrAdapterPass {
+    int32_t struct_size;            /* sizeof(GgrAdapterPass) */
+    int32_t reserved;               /* 0 */
+    int32_t num_cameras;            /* C */
+    int32_t gaussians_per_camera;   /* G */
+    int32_t samples_per_row;        /* consecutive Gaussians that share one raw row (>= 1) */
+    int32_t d_sh;                   /* 1, 4, 9, 16 or 25 */
+    float scale_min, scale_max, eps;
+    int32_t debug;                  /* != 0: synchronise after the launch and report its error */
+    int32_t reserved2;              /* 0 */
+    int32_t reserved3;              /* padding, not read */
+    const float* depth;             /* [C,G] */
+    const float* coords;            /* [C,G,2] normalised image coordinates */
+    const float* raw;               /* [C,G/samples_per_row,7+3*d_sh]: scale logits 3, quaternion xyzw 4, harmonics (xyz d_sh) */
+    const float* c2w;               /* [C,3,4] */
+    const float* Kinv;              /* [C,3,3] inverse normalised intrinsics */
+    const float* q_cam;             /* [C,4] (w,x,y,z) of c2w's rotation */
+    const float* scale_mult;        /* [C] */
+    const float* sh_transform;      /* [C,d_sh,d_sh]: the diagonal blocks are read */
+    const float* sh_mask;           /* [d_sh] */
+    float* out_means;               /* forward: [P,3] */
+    float* out_scales;              /* forward: [P,3] */
+    float* out_quats;               /* forward: [P,4] (w,x,y,z) */
+    float* out_harmonics;           /* forward: [P,3,d_sh] */
+    const float* dL_dmeans;         /* backward: shapes of the outputs */
+    const float* dL_dscales;
+    const float* dL_dquats;
+    const float* dL_dharmonics;
+    float* dL_draw;                 /* backward: shape of raw, written whole */
+    float* dL_ddepth;               /* backward: [C,G], written whole, or NULL */
+    float* dL_dcoords;              /* backward: [C,G,2], written whole, or NULL */
+    float* dL_dc2w;                 /* backward: [C,3,4] zero-initialised, added into, or NULL */
+    float* dL_dKinv;                /* backward: [C,3,3] likewise */
+    float* dL_dq_cam;               /* backward: [C,4] likewise */
+    float* dL_dscale_mult;          /* backward: [C] likewise */
+    float* dL_dsh_transform;        /* backward: [C,d_sh,d_sh] likewise (diagonal blocks) */
+} GgrAdapterPass;
+
+int ggr_adapter_forward(const GgrAdapterPass* pass, void* stream);
+int ggr_adapter_backward(const GgrAdapterPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
