@@ -206,6 +206,22 @@ def adapter_pass(**fields) -> GgrAdapterPass:
     return GgrAdapterPass(struct_size=C.sizeof(GgrAdapterPass), **fields)
 
 
+class GgrDepthHeadPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("num_cameras", C.c_int32), ("rays_per_camera", C.c_int32),
+                ("num_buckets", C.c_int32), ("num_surfaces", C.c_int32), ("samples_per_ray", C.c_int32), ("deterministic", C.c_int32),
+                ("use_transmittance", C.c_int32), ("xy_raw_stride", C.c_int32), ("debug", C.c_int32), ("reserved2", C.c_int32),
+                ("opacity_exponent", C.c_float), ("opacity_scale", C.c_float), ("inv_w", C.c_float), ("inv_h", C.c_float),
+                ("logits", C.c_void_p), ("xy_raw", C.c_void_p), ("ray_xy", C.c_void_p), ("near", C.c_void_p), ("far", C.c_void_p),
+                ("u", C.c_void_p), ("out_depth", C.c_void_p), ("out_opacity", C.c_void_p), ("out_coords", C.c_void_p),
+                ("index", C.c_void_p), ("dL_ddepth", C.c_void_p), ("dL_dopacity", C.c_void_p), ("dL_dcoords", C.c_void_p),
+                ("dL_dlogits", C.c_void_p), ("dL_dxy_raw", C.c_void_p)]
+
+
+def depth_head_pass(**fields) -> GgrDepthHeadPass:
+    """The argument of ggr_depth_head_forward / ggr_depth_head_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrDepthHeadPass(struct_size=C.sizeof(GgrDepthHeadPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -289,6 +305,8 @@ SYMBOLS = [
     ("ggr_projection_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrProjectionPass), C.c_void_p]),
     ("ggr_adapter_forward", C.c_int, [C.POINTER(GgrAdapterPass), C.c_void_p]),
     ("ggr_adapter_backward", C.c_int, [C.POINTER(GgrAdapterPass), C.c_void_p]),
+    ("ggr_depth_head_forward", C.c_int, [C.POINTER(GgrDepthHeadPass), C.c_void_p]),
+    ("ggr_depth_head_backward", C.c_int, [C.POINTER(GgrDepthHeadPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

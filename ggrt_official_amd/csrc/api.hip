@@ -15,6 +15,7 @@
 #include "blend_absgrad.h"
 #include "projection.h"
 #include "adapter.h"
+#include "depth_head.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1386,6 +1387,90 @@ int ggr_adapter_backward(const GgrAdapterPass* ap, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     ggr::launch_adapter_backward(a, s);
     KCHECK(ap->debug != 0, s, "adapter_backward");
+    return GGR_OK;
+}
+
+// ---- the depth-head pass (depth_head.hip): GGRt's depth sampling, depth and opacity, one forward and one backward launch ----------
+namespace {
+int depth_head_pass_check(const GgrDepthHeadPass* dp, bool backward, ggr::DepthHeadArgs* a) {
+    if (!dp) return fail(GGR_E_INVALID, "null GgrDepthHeadPass");
+    if (dp->struct_size < (int32_t)sizeof(GgrDepthHeadPass))
+        return fail(GGR_E_INVALID, "GgrDepthHeadPass.struct_size %d is smaller than the %d bytes of its fields", (int)dp->struct_size,
+                    (int)sizeof(GgrDepthHeadPass));
+    if (dp->reserved != 0 || dp->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrDepthHeadPass.reserved must be 0, not %d / %d", (int)dp->reserved, (int)dp->reserved2);
+    if (dp->num_cameras < 0 || dp->rays_per_camera < 0)
+        return fail(GGR_E_INVALID, "GgrDepthHeadPass: negative size (num_cameras %d, rays_per_camera %d)", (int)dp->num_cameras, (int)dp->rays_per_camera);
+    const int s = dp->num_buckets, srf = dp->num_surfaces, spp = dp->samples_per_ray;
+    if (s < 1) return fail(GGR_E_INVALID, "GgrDepthHeadPass.num_buckets must be at least 1, not %d", s);
+    if (s > ggr::kDepthHeadMaxBuckets) return fail(GGR_E_LIMIT, "GgrDepthHeadPass.num_buckets %d is above %d", s, ggr::kDepthHeadMaxBuckets);
+    if (spp < 1) return fail(GGR_E_INVALID, "GgrDepthHeadPass.samples_per_ray must be at least 1, not %d", spp);
+    if (spp > ggr::kDepthHeadMaxSamples) return fail(GGR_E_LIMIT, "GgrDepthHeadPass.samples_per_ray %d is above %d", spp, ggr::kDepthHeadMaxSamples);
+    if (dp->deterministic && spp > s)
+        return fail(GGR_E_INVALID, "GgrDepthHeadPass.samples_per_ray %d is above num_buckets %d in deterministic mode", spp, s);
+    if (srf < 1) return fail(GGR_E_INVALID, "GgrDepthHeadPass.num_surfaces must be at least 1, not %d", srf);
+    if (dp->xy_raw_stride < 2) return fail(GGR_E_INVALID, "GgrDepthHeadPass.xy_raw_stride must be at least 2, not %d", (int)dp->xy_raw_stride);
+    if ((int64_t)2 * s * srf >= 0x7FFFFFFFll) return fail(GGR_E_LIMIT, "GgrDepthHeadPass.num_surfaces %d: a logits row is too long", srf);
+    if (dp->num_cameras > 65535) return fail(GGR_E_LIMIT, "GgrDepthHeadPass.num_cameras: more than 65535 cameras");
+    // C·R·srf·spp < 2^31, factor by factor (no product may overflow on the way)
+    int64_t total = dp->num_cameras;
+    for (int64_t f : {(int64_t)dp->rays_per_camera, (int64_t)srf, (int64_t)spp}) {
+        total *= f;
+        if (total >= 0x7FFFFFFFll)
+            return fail(GGR_E_LIMIT, "GgrDepthHeadPass: num_cameras x rays_per_camera x num_surfaces x samples_per_ray too large");
+    }
+    const bool any = dp->num_cameras > 0 && dp->rays_per_camera > 0;
+    const void* need_in[] = {dp->logits, dp->xy_raw, dp->ray_xy, dp->near, dp->far};
+    const char* name_in[] = {"logits", "xy_raw", "ray_xy", "near", "far"};
+    for (int i = 0; i < 5; ++i)
+        if (any && !need_in[i]) return fail(GGR_E_INVALID, "GgrDepthHeadPass.%s is NULL", name_in[i]);
+    if (any && !backward) {
+        if (!dp->deterministic && !dp->u) return fail(GGR_E_INVALID, "GgrDepthHeadPass.u is NULL in sampled mode");
+        const void* need[] = {dp->out_depth, dp->out_opacity, dp->out_coords, dp->index};
+        const char* name[] = {"out_depth", "out_opacity", "out_coords", "index"};
+        for (int i = 0; i < 4; ++i)
+            if (!need[i]) return fail(GGR_E_INVALID, "GgrDepthHeadPass.%s is NULL", name[i]);
+    }
+    if (any && backward) {
+        if (!dp->index) return fail(GGR_E_INVALID, "GgrDepthHeadPass.index is NULL");
+        if (!dp->dL_dlogits) return fail(GGR_E_INVALID, "GgrDepthHeadPass.dL_dlogits is NULL");
+    }
+    const void* all[] = {dp->logits, dp->xy_raw, dp->ray_xy, dp->near, dp->far, dp->u, dp->out_depth, dp->out_opacity, dp->out_coords,
+                         dp->index, dp->dL_ddepth, dp->dL_dopacity, dp->dL_dcoords, dp->dL_dlogits, dp->dL_dxy_raw};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrDepthHeadPass: a buffer is misaligned (every array needs 4-byte alignment)");
+    a->C = dp->num_cameras; a->R = dp->rays_per_camera; a->s = s; a->srf = srf; a->spp = spp;
+    a->deterministic = dp->deterministic != 0; a->transmittance = dp->use_transmittance != 0; a->xy_stride = dp->xy_raw_stride;
+    a->exponent = dp->opacity_exponent; a->opacity_scale = dp->opacity_scale; a->inv_w = dp->inv_w; a->inv_h = dp->inv_h;
+    a->logits = dp->logits; a->xy_raw = dp->xy_raw; a->ray_xy = dp->ray_xy; a->near = dp->near; a->far = dp->far; a->u = dp->u;
+    a->depth = dp->out_depth; a->opacity = dp->out_opacity; a->coords = dp->out_coords; a->index = dp->index;
+    a->g_depth = dp->dL_ddepth; a->g_opacity = dp->dL_dopacity; a->g_coords = dp->dL_dcoords; a->g_logits = dp->dL_dlogits;
+    a->g_xy = dp->dL_dxy_raw;
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_depth_head_forward(const GgrDepthHeadPass* dp, void* stream) {
+    g_err[0] = 0;
+    ggr::DepthHeadArgs a;
+    const int rc = depth_head_pass_check(dp, false, &a);
+    if (rc) return rc;
+    if (a.C == 0 || a.R == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_depth_head_forward(a, s);
+    KCHECK(dp->debug != 0, s, "depth_head_forward");
+    return GGR_OK;
+}
+
+int ggr_depth_head_backward(const GgrDepthHeadPass* dp, void* stream) {
+    g_err[0] = 0;
+    ggr::DepthHeadArgs a;
+    const int rc = depth_head_pass_check(dp, true, &a);
+    if (rc) return rc;
+    if (a.C == 0 || a.R == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_depth_head_backward(a, s);
+    KCHECK(dp->debug != 0, s, "depth_head_backward");
     return GGR_OK;
 }
 

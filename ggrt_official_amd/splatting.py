@@ -277,6 +277,126 @@ def fused_gaussian_adapter(extrinsics: Tensor, intrinsics: Tensor, coordinates: 
     return Gaussians(means=means, covariances=None, harmonics=harmonics, opacities=None, scales=scales, rotations=quats)
 
 
+@dataclass
+class DepthHead:
+    """What ``fused_depth_head`` returns, per Gaussian p = c·G + (r·srf + j)·spp + k: the adapter's and the decoder's inputs."""
+    depths: Tensor         # [C, G]
+    opacities: Tensor      # [C, G]
+    coordinates: Tensor    # [C, G, 2]
+    index: Tensor          # [C, G] int32: the chosen depth bucket (no gradient)
+
+
+# tests only: True fills every buffer the depth-head launches must write whole with NaN (index: -1) before the launch
+_DEPTH_HEAD_POISON = False
+
+
+def _depth_head_buffer(shape, dtype, dev):
+    if _DEPTH_HEAD_POISON:
+        return torch.full(shape, -1 if dtype == torch.int32 else float("nan"), dtype=dtype, device=dev)
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
+class _FusedDepthHead(torch.autograd.Function):
+    """ggr_depth_head_forward / ggr_depth_head_backward (csrc/depth_head.hip) behind autograd: one launch each way.  `xy_raw` arrives
+    as [C, R·srf, 2] with a unit inner stride and one common row stride (read in place)."""
+
+    @staticmethod
+    def forward(ctx, logits, xy_raw, ray_xy, near, far, u, dims):
+        dev = logits.device
+        n_cam, rays, s, srf, spp, deterministic, transmittance, exponent, scale, inv_w, inv_h = dims
+        g = rays * srf * spp
+        depth, opacity = _depth_head_buffer((n_cam, g), torch.float32, dev), _depth_head_buffer((n_cam, g), torch.float32, dev)
+        coords, index = _depth_head_buffer((n_cam, g, 2), torch.float32, dev), _depth_head_buffer((n_cam, g), torch.int32, dev)
+        ctx.dims = dims
+        ctx.set_materialize_grads(False)     # (an output nobody used arrives as None and goes to the launch as NULL)
+        dp = _FusedDepthHead._pass(dims, logits, xy_raw, ray_xy, near, far, index, u=None if u is None else u.data_ptr(),
+                                   out_depth=depth.data_ptr(), out_opacity=opacity.data_ptr(), out_coords=coords.data_ptr())
+        with torch.cuda.device(dev):
+            rc = _lib.load().ggr_depth_head_forward(C.byref(dp), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"ggr_depth_head_forward failed (code {rc}): {_lib.last_error()}")
+        ctx.save_for_backward(logits, xy_raw, ray_xy, near, far, index)
+        ctx.mark_non_differentiable(index)
+        return depth, opacity, coords, index
+
+    @staticmethod
+    def _pass(dims, logits, xy_raw, ray_xy, near, far, index, **more):
+        n_cam, rays, s, srf, spp, deterministic, transmittance, exponent, scale, inv_w, inv_h = dims
+        stride = xy_raw.stride(1) if xy_raw.shape[1] > 1 else max(2, xy_raw.stride(1))
+        return _lib.depth_head_pass(reserved=0, num_cameras=n_cam, rays_per_camera=rays, num_buckets=s, num_surfaces=srf,
+                                    samples_per_ray=spp, deterministic=int(deterministic), use_transmittance=int(transmittance),
+                                    xy_raw_stride=stride, debug=0, reserved2=0, opacity_exponent=exponent, opacity_scale=scale,
+                                    inv_w=inv_w, inv_h=inv_h, logits=logits.data_ptr(), xy_raw=xy_raw.data_ptr(),
+                                    ray_xy=ray_xy.data_ptr(), near=near.data_ptr(), far=far.data_ptr(), index=index.data_ptr(), **more)
+
+    @staticmethod
+    def backward(ctx, g_depth, g_opacity, g_coords, _g_index):
+        logits, xy_raw, ray_xy, near, far, index = ctx.saved_tensors
+        dev = logits.device
+        ptr = lambda t: None if t is None else t.data_ptr()
+        f = lambda t: None if t is None else t.to(dtype=torch.float32).contiguous()
+        g_depth, g_opacity, g_coords = f(g_depth), f(g_opacity), f(g_coords)
+        d_logits = _depth_head_buffer(tuple(logits.shape), torch.float32, dev)
+        d_xy = _depth_head_buffer(tuple(xy_raw.shape), torch.float32, dev) if ctx.needs_input_grad[1] else None
+        dp = _FusedDepthHead._pass(ctx.dims, logits, xy_raw, ray_xy, near, far, index, dL_ddepth=ptr(g_depth),
+                                   dL_dopacity=ptr(g_opacity), dL_dcoords=ptr(g_coords), dL_dlogits=d_logits.data_ptr(),
+                                   dL_dxy_raw=ptr(d_xy))
+        with torch.cuda.device(dev):
+            rc = _lib.load().ggr_depth_head_backward(C.byref(dp), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"ggr_depth_head_backward failed (code {rc}): {_lib.last_error()}")
+        return d_logits if ctx.needs_input_grad[0] else None, d_xy, None, None, None, None, None
+
+
+def fused_depth_head(logits: Tensor, xy_raw: Tensor, ray_xy: Tensor, near: Tensor, far: Tensor, image_shape, num_surfaces: int,
+                     samples_per_ray: int, deterministic: bool, *, use_transmittance: bool = False, opacity_exponent: float = 1.0,
+                     opacity_scale: Optional[float] = None, u: Optional[Tensor] = None) -> DepthHead:
+    """GGRt's ``DepthPredictorMonocular.forward`` after its projection, ``map_pdf_to_opacity`` / gaussians_per_pixel and the
+    pixel-offset lines of ``EncoderEpipolar.forward`` as one HIP launch, and one more for the backward (the
+    arithmetic: ``GgrDepthHeadPass`` in include/ggr_raster.h).  C = b·v cameras of R rays: ``logits`` [C,R,2·s·srf] is
+    ``depth_predictor.projection``'s output in its own channel order ``(dpt srf c)``; ``xy_raw`` [C,R·srf,2] (or [C,R,srf,2]) the
+    first two channels of the ``to_gaussians`` rows — a view whose rows have one common stride and a unit inner stride, such as
+    ``rows[..., :2]``, is read in place, anything else is made contiguous; ``ray_xy`` [R,2] the normalised pixel centres;
+    ``near`` / ``far`` [C]; ``image_shape`` (h, w) gives the pixel size.  ``deterministic``: the ``samples_per_ray`` buckets of
+    largest pdf, ties to the lower bucket; otherwise one bucket per uniform number of ``u`` [C,R,srf,spp] (``None``: drawn here
+    with ``torch.rand`` on the device — the kernel draws nothing).  ``opacity_exponent`` is the reference's ``2**x`` for the
+    current ``global_step``; ``opacity_scale=None`` means ``1 / samples_per_ray``.  Returns ``DepthHead`` with G = R·srf·spp
+    Gaussians per camera, sample axis innermost: what ``fused_gaussian_adapter(ext, intr, coordinates, depths, rows[..., 2:], …)``
+    and the decoder's ``opacities`` (``.reshape(b, -1)``, a view) take.  Gradients reach ``logits`` and ``xy_raw``; the choice
+    of ``index`` is not differentiated and ``near``, ``far``, ``ray_xy``, ``u`` get none."""
+    dev = logits.device
+    if dev.type != "cuda":
+        raise RuntimeError("fused_depth_head runs on the GPU only (there is no CPU fallback)")
+    srf, spp = int(num_surfaces), int(samples_per_ray)
+    if logits.dim() != 3 or srf < 1 or logits.shape[-1] % (2 * srf) != 0 or logits.shape[-1] == 0:
+        raise ValueError(f"logits {tuple(logits.shape)} is not [C, R, 2*s*{srf}]")
+    n_cam, rays, width = logits.shape
+    s = width // (2 * srf)
+    if tuple(xy_raw.shape) not in ((n_cam, rays * srf, 2), (n_cam, rays, srf, 2)):
+        raise ValueError(f"xy_raw {tuple(xy_raw.shape)} is neither [{n_cam}, {rays * srf}, 2] nor [{n_cam}, {rays}, {srf}, 2]")
+    if tuple(ray_xy.shape) != (rays, 2) or near.numel() != n_cam or far.numel() != n_cam:
+        raise ValueError("ray_xy must be [R, 2], near and far [C]")
+    h, w = image_shape
+    f = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    logits = f(logits)
+    xy_raw = xy_raw.to(device=dev, dtype=torch.float32).reshape(n_cam, rays * srf, 2)
+    if not (xy_raw.stride(2) == 1 and xy_raw.stride(1) >= 2 and (n_cam < 2 or xy_raw.stride(0) == xy_raw.stride(1) * rays * srf)):
+        xy_raw = xy_raw.contiguous()
+    if not deterministic:
+        if u is None:
+            u = torch.rand((n_cam, rays, srf, spp), dtype=torch.float32, device=dev)
+        if u.numel() != n_cam * rays * srf * spp:
+            raise ValueError(f"u {tuple(u.shape)} is not [{n_cam}, {rays}, {srf}, {spp}]")
+        u = f(u.detach())
+    else:
+        u = None
+    scale = 1.0 / spp if opacity_scale is None else float(opacity_scale)
+    dims = (n_cam, rays, s, srf, spp, bool(deterministic), bool(use_transmittance), float(opacity_exponent), scale, 1.0 / w, 1.0 / h)
+    depth, opacity, coords, index = _FusedDepthHead.apply(logits, xy_raw, f(ray_xy.detach()), f(near.detach().reshape(-1)),
+                                                          f(far.detach().reshape(-1)), u, dims)
+    return DepthHead(depths=depth, opacities=opacity, coordinates=coords, index=index)
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

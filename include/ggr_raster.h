@@ -874,6 +874,80 @@ typedef struct GgrAdapterPass {
 int ggr_adapter_forward(const GgrAdapterPass* pass, void* stream);
 int ggr_adapter_backward(const GgrAdapterPass* pass, void* stream);
 
+/* ---- the depth-head pass: GGRt's depth sampling, depth and opacity in one forward and one backward launch (ABI 11, additive) -----
+ * What GGRt does between `depth_predictor.projection` and GaussianAdapter.forward with about 25 torch launches each way
+ * (DepthPredictorMonocular.forward, map_pdf_to_opacity and the pixel-offset lines of EncoderEpipolar.forward).  Its results —
+ * depth, opacity, coords — are the per-Gaussian inputs of GgrAdapterPass and of the decoder, in the same grouping: C cameras, each
+ * with R rays x srf surfaces x spp samples, G = R*srf*spp Gaussians per camera with the sample axis innermost, row
+ * p = c*G + (r*srf + j)*spp + k.
+ * Inputs.  logits [C,R,2*s*srf], dense: the projection's output in GGRt's own channel order (bucket, surface, {pdf, offset}):
+ * for ray r, surface j, bucket d the pdf logit is element (d*srf + j)*2 and the offset logit element (d*srf + j)*2 + 1.
+ * xy_raw: two floats per (c, r, j) at float offset (c*R*srf + r*srf + j)*xy_raw_stride (xy_raw_stride >= 2: the first two
+ * channels of a wider row are read in place).  ray_xy [R,2]: normalised pixel centres, shared by all cameras.  near [C], far [C].
+ * u [C,G]: uniform random numbers in [0, 1), DRAWN BY THE CALLER; read only when `deterministic` is 0 (may be NULL otherwise).
+ * Per (c, r, j), all in float32:
+ *     pdf  = softmax(pdf logits) over the s buckets;   npdf = pdf / (FLT_EPSILON + sum(pdf))
+ *     index_k = deterministic ? the bucket of (k+1)-th largest pdf, TIES GOING TO THE LOWER BUCKET (so index_0..spp-1 are distinct)
+ *                             : min(#{d : cdf_d <= u_k}, s - 1), cdf the running sum of npdf in bucket order — searchsorted(right)
+ *                               and a clip; samples are independent: a bucket may be drawn more than once
+ *     rel     = (index_k + sigmoid(offset logit at index_k)) / s
+ *     depth_k = 1 / ((1 - rel)*(1/(near+e) - 1/(far+e)) + 1/(far+e) + e),  e = 1e-10
+ *     q_k     = use_transmittance ? pdf_i / (1 - sum_{d<i} pdf_d + 1e-10) : npdf_i,   i = index_k
+ *     opacity_k = opacity_scale * 0.5*(1 - max(1 - q_k, 0)^opacity_exponent + q_k^(1/opacity_exponent));
+ *                 opacity_exponent == 1: exactly opacity_scale * q_k, no pow
+ *     coords_k  = ray_xy[r] + (sigmoid(xy_raw) - 0.5) * (inv_w, inv_h), the same for the spp samples
+ * The max(.., 0) is the one deviation from GGRt: the transmittance form can round q above 1 at the last bucket, where
+ * GGRt's (1 - q)^exponent is NaN.  opacity_exponent is GGRt's 2**x, computed by the host from global_step; opacity_scale its
+ * 1 / gaussians_per_pixel.  ggr_depth_head_forward writes every element of out_depth, out_opacity, out_coords and index.
+ * ggr_depth_head_backward takes dL_ddepth, dL_dopacity, dL_dcoords (each may be NULL: taken as zero), the forward's inputs and
+ * `index` (read, not recomputed: u is not needed), recomputes the softmax, and writes EVERY element of dL_dlogits (the pdf
+ * channels: the softmax's backward of the gradient at the chosen buckets, npdf's normalisation and the transmittance's prefix sum
+ * included; the offset channels: zero except at the chosen buckets) and of dL_dxy_raw (dense [C,R*srf,2], summed over the
+ * samples; may be NULL: not computed).  The choice of index is not differentiated; near, far, ray_xy and u get no gradient.
+ * One lane owns one (c, r, j): repeated indices are summed in registers, there are no atomics, and two runs give identical bits.
+ * All arrays are float32 (index: int32) on the device and need 4-byte alignment.  Both calls allocate nothing, read nothing
+ * back, do not synchronise (unless `debug`) and are hipGraph-capturable; num_cameras == 0 or rays_per_camera == 0 is valid and
+ * enqueues nothing.  GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero
+ * `reserved`, a negative size, num_buckets / num_surfaces / samples_per_ray below 1, samples_per_ray above num_buckets when
+ * deterministic, xy_raw_stride below 2, a misaligned buffer, or (unless the call is empty) a NULL required pointer — u counts as
+ * required when not deterministic; GGR_E_LIMIT for num_buckets > 64, samples_per_ray > 16, more than 65535 cameras, 2^31 - 1
+ * or more Gaussians, or a logits row (2*s*srf floats) of 2^31 floats or more. */
+typedef struct GgrDepthHeadPass {
+    int32_t struct_size;            /* sizeof(GgrDepthHeadPass) */
+    int32_t reserved;               /* 0 */
+    int32_t num_cameras;            /* C */
+    int32_t rays_per_camera;        /* R */
+    int32_t num_buckets;            /* s: 1..64 */
+    int32_t num_surfaces;           /* srf >= 1 */
+    int32_t samples_per_ray;        /* spp: 1..16 (<= s when deterministic) */
+    int32_t deterministic;          /* != 0: the spp buckets of largest pdf; 0: sampled with u */
+    int32_t use_transmittance;      /* != 0: q = pdf_i / (1 - sum_{d<i} pdf_d + 1e-10) */
+    int32_t xy_raw_stride;          /* floats between consecutive (c, r, j) rows of xy_raw (>= 2) */
+    int32_t debug;                  /* != 0: synchronise after the launch and report its error */
+    int32_t reserved2;              /* 0 */
+    float opacity_exponent;         /* GGRt's 2**x (> 0) */
+    float opacity_scale;            /* 1 / gaussians_per_pixel */
+    float inv_w, inv_h;             /* GGRt's pixel_size */
+    const float* logits;            /* [C,R,2*s*srf] */
+    const float* xy_raw;            /* two floats per (c, r, j), rows xy_raw_stride floats apart */
+    const float* ray_xy;            /* [R,2] */
+    const float* near;              /* [C] */
+    const float* far;               /* [C] */
+    const float* u;                 /* [C,G] uniform numbers (sampled mode), or NULL when deterministic */
+    float* out_depth;               /* forward: [C,G] */
+    float* out_opacity;             /* forward: [C,G] */
+    float* out_coords;              /* forward: [C,G,2] */
+    int32_t* index;                 /* [C,G]: written by the forward, read by the backward */
+    const float* dL_ddepth;         /* backward: [C,G], or NULL */
+    const float* dL_dopacity;       /* backward: [C,G], or NULL */
+    const float* dL_dcoords;        /* backward: [C,G,2], or NULL */
+    float* dL_dlogits;              /* backward: shape of logits, written whole */
+    float* dL_dxy_raw;              /* backward: [C,R*srf,2] dense, written whole, or NULL */
+} GgrDepthHeadPass;
+
+int ggr_depth_head_forward(const GgrDepthHeadPass* pass, void* stream);
+int ggr_depth_head_backward(const GgrDepthHeadPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
