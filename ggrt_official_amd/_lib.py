@@ -222,6 +222,26 @@ def depth_head_pass(**fields) -> GgrDepthHeadPass:
     return GgrDepthHeadPass(struct_size=C.sizeof(GgrDepthHeadPass), **fields)
 
 
+class GgrEpipolarPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int32), ("num_views", C.c_int32),
+                ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("num_samples", C.c_int32),
+                ("use_window", C.c_int32), ("window_y0", C.c_int32), ("window_y1", C.c_int32), ("window_x0", C.c_int32),
+                ("window_x1", C.c_int32), ("debug", C.c_int32), ("image_strides", C.c_int64 * 5),
+                ("c2w", C.c_void_p), ("w2c", C.c_void_p), ("K", C.c_void_p), ("Kinv", C.c_void_p), ("near", C.c_void_p),
+                ("far", C.c_void_p), ("images", C.c_void_p), ("features", C.c_void_p), ("valid", C.c_void_p), ("xy_ray", C.c_void_p),
+                ("xy_sample", C.c_void_p), ("xy_sample_near", C.c_void_p), ("xy_sample_far", C.c_void_p), ("origins", C.c_void_p),
+                ("directions", C.c_void_p), ("depth", C.c_void_p), ("segment", C.c_void_p), ("dL_dfeatures", C.c_void_p),
+                ("dL_dimages", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
+def epipolar_pass(**fields) -> GgrEpipolarPass:
+    """The argument of ggr_epipolar_forward / ggr_epipolar_backward (include/ggr_raster.h), struct_size filled in;
+    `image_strides` may be any sequence of five integers."""
+    if "image_strides" in fields:
+        fields["image_strides"] = (C.c_int64 * 5)(*fields["image_strides"])
+    return GgrEpipolarPass(struct_size=C.sizeof(GgrEpipolarPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -307,6 +327,9 @@ SYMBOLS = [
     ("ggr_adapter_backward", C.c_int, [C.POINTER(GgrAdapterPass), C.c_void_p]),
     ("ggr_depth_head_forward", C.c_int, [C.POINTER(GgrDepthHeadPass), C.c_void_p]),
     ("ggr_depth_head_backward", C.c_int, [C.POINTER(GgrDepthHeadPass), C.c_void_p]),
+    ("ggr_epipolar_scratch_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("ggr_epipolar_forward", C.c_int, [C.POINTER(GgrEpipolarPass), C.c_void_p]),
+    ("ggr_epipolar_backward", C.c_int, [C.POINTER(GgrEpipolarPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

@@ -16,6 +16,7 @@
 #include "projection.h"
 #include "adapter.h"
 #include "depth_head.h"
+#include "epipolar.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1471,6 +1472,104 @@ int ggr_depth_head_backward(const GgrDepthHeadPass* dp, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     ggr::launch_depth_head_backward(a, s);
     KCHECK(dp->debug != 0, s, "depth_head_backward");
+    return GGR_OK;
+}
+
+// ---- the epipolar-sampler pass (epipolar.hip): GGRt's EpipolarSampler.forward and the depth lines behind it ---------------------
+namespace {
+int64_t epipolar_scratch_bytes(int64_t b, int64_t v, int64_t c, int64_t h, int64_t w) {
+    if (b < 0 || v < ggr::kEpipolarMinViews || v > ggr::kEpipolarMaxViews || c < 1 || c > ggr::kEpipolarMaxChannels || h < 1 || w < 1) return -1;
+    if (b * v > 65535) return -1;
+    const int64_t pixels = b * v * h;            // < 2^16 · 2^31
+    if (pixels >= 0x7FFFFFFFll || pixels * w >= 0x7FFFFFFFll) return -1;
+    return pixels * w * c * (int64_t)sizeof(float);
+}
+
+int epipolar_pass_check(const GgrEpipolarPass* ep, bool backward, ggr::EpipolarArgs* a) {
+    if (!ep) return fail(GGR_E_INVALID, "null GgrEpipolarPass");
+    if (ep->struct_size < (int32_t)sizeof(GgrEpipolarPass))
+        return fail(GGR_E_INVALID, "GgrEpipolarPass.struct_size %d is smaller than the %d bytes of its fields", (int)ep->struct_size,
+                    (int)sizeof(GgrEpipolarPass));
+    if (ep->reserved != 0) return fail(GGR_E_INVALID, "GgrEpipolarPass.reserved must be 0, not %d", (int)ep->reserved);
+    const int b = ep->batch, v = ep->num_views, c = ep->channels, h = ep->height, w = ep->width, s = ep->num_samples;
+    if (b < 0) return fail(GGR_E_INVALID, "GgrEpipolarPass.batch is negative (%d)", b);
+    if (s < 1 || s > ggr::kEpipolarMaxSamples) return fail(GGR_E_INVALID, "GgrEpipolarPass.num_samples %d is outside 1..%d", s, ggr::kEpipolarMaxSamples);
+    if (c < 1 || c > ggr::kEpipolarMaxChannels) return fail(GGR_E_INVALID, "GgrEpipolarPass.channels %d is outside 1..%d", c, ggr::kEpipolarMaxChannels);
+    if (v < ggr::kEpipolarMinViews || v > ggr::kEpipolarMaxViews)
+        return fail(GGR_E_INVALID, "GgrEpipolarPass.num_views %d is outside %d..%d", v, ggr::kEpipolarMinViews, ggr::kEpipolarMaxViews);
+    if (h < 1 || w < 1) return fail(GGR_E_INVALID, "GgrEpipolarPass.height / width must be at least 1, not %d x %d", h, w);
+    int y0 = 0, y1 = h, x0 = 0, x1 = w;
+    if (ep->use_window) {
+        y0 = ep->window_y0; y1 = ep->window_y1; x0 = ep->window_x0; x1 = ep->window_x1;
+        if (y0 < 0 || y0 >= y1 || y1 > h || x0 < 0 || x0 >= x1 || x1 > w)
+            return fail(GGR_E_INVALID, "GgrEpipolarPass: the window rows %d..%d, columns %d..%d is empty or leaves the %d x %d grid", y0, y1, x0, x1, h, w);
+    }
+    const int64_t need = epipolar_scratch_bytes(b, v, c, h, w);
+    if (need < 0) return fail(GGR_E_INVALID, "GgrEpipolarPass: too large (batch x num_views above 65535, or 2^31 map pixels or more)");
+    int64_t total = (int64_t)b * v * (v - 1);      // < 2^16 · 8
+    for (int64_t f : {(int64_t)(y1 - y0), (int64_t)(x1 - x0), (int64_t)s}) {
+        total *= f;
+        if (total >= 0x7FFFFFFFll) return fail(GGR_E_INVALID, "GgrEpipolarPass: too large (2^31 or more of pair-rays x samples)");
+    }
+    const bool any = b > 0;
+    if (any && !backward) {
+        const void* need_in[] = {ep->c2w, ep->w2c, ep->K, ep->Kinv, ep->near, ep->far};
+        const char* name_in[] = {"c2w", "w2c", "K", "Kinv", "near", "far"};
+        for (int i = 0; i < 6; ++i)
+            if (!need_in[i]) return fail(GGR_E_INVALID, "GgrEpipolarPass.%s is NULL", name_in[i]);
+        if (ep->features && !ep->images) return fail(GGR_E_INVALID, "GgrEpipolarPass.images is NULL");
+        if (ep->features && !ep->scratch) return fail(GGR_E_INVALID, "GgrEpipolarPass.scratch is NULL");
+    }
+    if (any && backward) {
+        const void* need_in[] = {ep->valid, ep->segment, ep->dL_dfeatures, ep->dL_dimages, ep->scratch};
+        const char* name_in[] = {"valid", "segment", "dL_dfeatures", "dL_dimages", "scratch"};
+        for (int i = 0; i < 5; ++i)
+            if (!need_in[i]) return fail(GGR_E_INVALID, "GgrEpipolarPass.%s is NULL", name_in[i]);
+    }
+    if (any && (backward || ep->features) && ep->scratch_bytes < need)
+        return fail(GGR_E_INVALID, "GgrEpipolarPass.scratch_bytes %lld is below the %lld bytes needed", (long long)ep->scratch_bytes, (long long)need);
+    const void* all[] = {ep->c2w, ep->w2c, ep->K, ep->Kinv, ep->near, ep->far, ep->images, ep->features, ep->xy_ray, ep->xy_sample,
+                         ep->xy_sample_near, ep->xy_sample_far, ep->origins, ep->directions, ep->depth, ep->segment, ep->dL_dfeatures,
+                         ep->dL_dimages, ep->scratch};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrEpipolarPass: a buffer is misaligned (every float array needs 4-byte alignment)");
+    a->b = b; a->v = v; a->c = c; a->h = h; a->w = w; a->s = s;
+    a->y0 = y0; a->y1 = y1; a->x0 = x0; a->x1 = x1;
+    a->img_sb = ep->image_strides[0]; a->img_sv = ep->image_strides[1]; a->img_sc = ep->image_strides[2];
+    a->img_sh = ep->image_strides[3]; a->img_sw = ep->image_strides[4];
+    a->c2w = ep->c2w; a->w2c = ep->w2c; a->K = ep->K; a->Kinv = ep->Kinv; a->near = ep->near; a->far = ep->far; a->images = ep->images;
+    a->features = ep->features; a->valid = ep->valid; a->xy_ray = ep->xy_ray; a->xy_sample = ep->xy_sample;
+    a->xy_near = ep->xy_sample_near; a->xy_far = ep->xy_sample_far; a->origins = ep->origins; a->directions = ep->directions;
+    a->depth = ep->depth; a->seg = ep->segment; a->g_features = ep->dL_dfeatures; a->g_images = ep->dL_dimages; a->scratch = ep->scratch;
+    return GGR_OK;
+}
+}  // namespace
+
+int64_t ggr_epipolar_scratch_bytes(int32_t batch, int32_t num_views, int32_t channels, int32_t height, int32_t width) {
+    return epipolar_scratch_bytes(batch, num_views, channels, height, width);
+}
+
+int ggr_epipolar_forward(const GgrEpipolarPass* ep, void* stream) {
+    g_err[0] = 0;
+    ggr::EpipolarArgs a;
+    const int rc = epipolar_pass_check(ep, false, &a);
+    if (rc) return rc;
+    if (a.b == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_epipolar_forward(a, s);
+    KCHECK(ep->debug != 0, s, "epipolar_forward");
+    return GGR_OK;
+}
+
+int ggr_epipolar_backward(const GgrEpipolarPass* ep, void* stream) {
+    g_err[0] = 0;
+    ggr::EpipolarArgs a;
+    const int rc = epipolar_pass_check(ep, true, &a);
+    if (rc) return rc;
+    if (a.b == 0) return GGR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_epipolar_backward(a, s);
+    KCHECK(ep->debug != 0, s, "epipolar_backward");
     return GGR_OK;
 }
 

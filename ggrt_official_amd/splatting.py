@@ -397,6 +397,115 @@ def fused_depth_head(logits: Tensor, xy_raw: Tensor, ray_xy: Tensor, near: Tenso
     return DepthHead(depths=depth, opacities=opacity, coordinates=coords, index=index)
 
 
+@dataclass
+class EpipolarSamples:
+    """What ``fused_epipolar_sampler`` returns: the fields of the reference's ``EpipolarSampling`` and ``depth``."""
+    features: Tensor         # [b, v, v-1, r, s, c]   (differentiable with respect to the feature maps)
+    valid: Tensor            # [b, v, v-1, r] bool
+    xy_ray: Tensor           # [b, v, r, 2]
+    xy_sample: Tensor        # [b, v, v-1, r, s, 2]
+    xy_sample_near: Tensor   # [b, v, v-1, r, s, 2]
+    xy_sample_far: Tensor    # [b, v, v-1, r, s, 2]
+    origins: Tensor          # [b, v, r, 3]
+    directions: Tensor       # [b, v, r, 3]
+    depth: Tensor            # [b, v, v-1, r, s]: the relative disparity that the depth encoding takes
+
+
+def _epipolar_check(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed (code {rc}): {_lib.last_error()}")
+
+
+class _FusedEpipolarSampler(torch.autograd.Function):
+    """ggr_epipolar_forward / ggr_epipolar_backward (csrc/epipolar.hip) behind autograd.  `images` [b,v,c,h,w] is read through
+    its strides; the cameras arrive detached, float32 and contiguous."""
+
+    @staticmethod
+    def forward(ctx, images, c2w, w2c, K, Kinv, near, far, dims):
+        dev = images.device
+        b, v, c, h, w, s, window = dims
+        r = h * w if window is None else (window[1] - window[0]) * (window[3] - window[2])
+        pairs = (b, v, v - 1, r)
+        new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        out = dict(features=new(pairs + (s, c)), valid=new(pairs, torch.uint8), xy_ray=new((b, v, r, 2)), xy_sample=new(pairs + (s, 2)),
+                   xy_sample_near=new(pairs + (s, 2)), xy_sample_far=new(pairs + (s, 2)), origins=new((b, v, r, 3)),
+                   directions=new((b, v, r, 3)), depth=new(pairs + (s,)), segment=new(pairs + (4,)))
+        lib = _lib.load()
+        nbytes = max(int(lib.ggr_epipolar_scratch_bytes(b, v, c, h, w)), 0)
+        scratch = new((nbytes // 4,))
+        ep = _FusedEpipolarSampler._pass(dims, images=images.data_ptr(), image_strides=images.stride(), c2w=c2w.data_ptr(),
+                                         w2c=w2c.data_ptr(), K=K.data_ptr(), Kinv=Kinv.data_ptr(), near=near.data_ptr(),
+                                         far=far.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=nbytes,
+                                         **{k: t.data_ptr() for k, t in out.items()})
+        with torch.cuda.device(dev):
+            _epipolar_check(lib.ggr_epipolar_forward(C.byref(ep), torch.cuda.current_stream(dev).cuda_stream), "ggr_epipolar_forward")
+        ctx.dims = dims
+        ctx.save_for_backward(out["valid"], out["segment"])
+        rest = tuple(out[k] for k in ("valid", "xy_ray", "xy_sample", "xy_sample_near", "xy_sample_far", "origins", "directions", "depth"))
+        ctx.mark_non_differentiable(*rest)
+        return (out["features"],) + rest
+
+    @staticmethod
+    def _pass(dims, **more):
+        b, v, c, h, w, s, window = dims
+        y0, y1, x0, x1 = window if window is not None else (0, 0, 0, 0)
+        return _lib.epipolar_pass(reserved=0, batch=b, num_views=v, channels=c, height=h, width=w, num_samples=s,
+                                  use_window=int(window is not None), window_y0=y0, window_y1=y1, window_x0=x0, window_x1=x1, debug=0, **more)
+
+    @staticmethod
+    def backward(ctx, g_features, *_others):
+        valid, segment = ctx.saved_tensors
+        b, v, c, h, w, s, window = ctx.dims
+        dev = valid.device
+        g_features = g_features.to(dtype=torch.float32).contiguous()
+        d_images = torch.empty((b, v, c, h, w), dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        nbytes = max(int(lib.ggr_epipolar_scratch_bytes(b, v, c, h, w)), 0)
+        scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        ep = _FusedEpipolarSampler._pass(ctx.dims, valid=valid.data_ptr(), segment=segment.data_ptr(), dL_dfeatures=g_features.data_ptr(),
+                                         dL_dimages=d_images.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=nbytes)
+        with torch.cuda.device(dev):
+            _epipolar_check(lib.ggr_epipolar_backward(C.byref(ep), torch.cuda.current_stream(dev).cuda_stream), "ggr_epipolar_backward")
+        return d_images, None, None, None, None, None, None, None
+
+
+def fused_epipolar_sampler(images: Tensor, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, num_samples: int,
+                           ray_window=None) -> EpipolarSamples:
+    """GGRt's ``EpipolarSampler.forward`` and the depth lines of ``EpipolarTransformer.forward`` (``get_depth``, the clip to
+    [near, far], ``depth_to_relative_disparity``) as HIP launches (the arithmetic: ``GgrEpipolarPass`` in
+    include/ggr_raster.h).  ``images`` [b,v,c,h,w] are the (downscaled) feature maps, ``extrinsics`` [b,v,4,4] camera-to-world,
+    ``intrinsics`` [b,v,3,3] normalised, ``near`` / ``far`` [b,v].  ``ray_window`` = (y0, y1, x0, x1) in ray-grid units casts only
+    the rays of that sub-rectangle of every view (the reference's ``crop_size`` path: rows ``h//crop*clip_h`` to
+    ``h//crop*(clip_h+1)``, columns alike); the feature maps stay whole.  Returns ``EpipolarSamples``: ``features`` is
+    differentiable with respect to ``images`` (one scatter launch, float atomics: reproducible up to summation order);
+    everything else is returned detached.  Camera gradients are not implemented: a camera tensor that requires grad raises.
+    ``images`` may be any float32 view (it is read through its strides); another dtype is converted once."""
+    dev = images.device
+    if dev.type != "cuda":
+        raise RuntimeError("fused_epipolar_sampler runs on the GPU only (there is no CPU fallback)")
+    for name, t in (("extrinsics", extrinsics), ("intrinsics", intrinsics), ("near", near), ("far", far)):
+        if t.requires_grad:
+            raise RuntimeError(f"fused_epipolar_sampler: {name} requires grad, but camera gradients are not implemented here "
+                               "(GGRt detaches its context poses; detach the cameras, near and far)")
+    if images.dim() != 5:
+        raise ValueError(f"images {tuple(images.shape)} is not [b, v, c, h, w]")
+    b, v, c, h, w = images.shape
+    if tuple(extrinsics.shape) != (b, v, 4, 4) or tuple(intrinsics.shape) != (b, v, 3, 3) or tuple(near.shape) != (b, v) or tuple(far.shape) != (b, v):
+        raise ValueError(f"extrinsics must be [{b}, {v}, 4, 4], intrinsics [{b}, {v}, 3, 3], near and far [{b}, {v}]")
+    window = None if ray_window is None else tuple(int(q) for q in ray_window)
+    if window is not None and not (len(window) == 4 and 0 <= window[0] < window[1] <= h and 0 <= window[2] < window[3] <= w):
+        raise ValueError(f"ray_window {window} is not (y0, y1, x0, x1) inside the {h} x {w} ray grid")
+    if images.dtype != torch.float32:
+        images = images.to(dtype=torch.float32)
+    f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    c2w, K = f(extrinsics), f(intrinsics)
+    w2c, Kinv = torch.linalg.inv(c2w).contiguous(), torch.linalg.inv(K).contiguous()
+    dims = (b, v, c, h, w, int(num_samples), window)
+    out = _FusedEpipolarSampler.apply(images, c2w, w2c, K, Kinv, f(near), f(far), dims)
+    return EpipolarSamples(features=out[0], valid=out[1].bool(), xy_ray=out[2], xy_sample=out[3], xy_sample_near=out[4],
+                           xy_sample_far=out[5], origins=out[6], directions=out[7], depth=out[8])
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

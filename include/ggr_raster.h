@@ -948,6 +948,96 @@ typedef struct GgrDepthHeadPass {
 int ggr_depth_head_forward(const GgrDepthHeadPass* pass, void* stream);
 int ggr_depth_head_backward(const GgrDepthHeadPass* pass, void* stream);
 
+/* ---- the epipolar-sampler pass: GGRt's EpipolarSampler.forward and the depth lines of EpipolarTransformer.forward (ABI 11, additive)
+ * The key/value tensor of GGRt's epipolar cross-attention and everything computed on the way to it: the reference's
+ * generate_image_rays, project_rays (near and far given), the sample points, the transpose -> grid_sample -> transpose of the
+ * other views' feature maps, the validity mask, and get_depth -> clip -> depth_to_relative_disparity — about a hundred small
+ * launches and eight full-size passes there, a layout launch and ONE main launch here; the backward scatters dL/dfeatures into
+ * the feature maps.
+ * Sizes: b batches, v views (2..8), c channels (1..512), feature maps h x w, s = num_samples (1..64).  The rays of every view are
+ * the pixel centres of the window rows window_y0..window_y1-1, columns window_x0..window_x1-1 when use_window != 0 (the
+ * reference's crop_size / clip_h / clip_w path), of the whole h x w grid otherwise; r rays, x fastest.  A pair-ray is
+ * (bi, vi, ov, ri), ov < v-1; it samples view o = ov + (ov >= vi).  P = b*v*(v-1)*r pair-rays in that order.
+ * Inputs (device, float32): c2w [b,v,4,4] camera-to-world; w2c [b,v,4,4] its inverse; K [b,v,3,3] normalised intrinsics; Kinv
+ * [b,v,3,3] its inverse (the two inverses come from the caller: they are tiny); near [b,v], far [b,v]; images: element
+ * (bi, vi, ch, y, x) at float offset bi*image_strides[0] + vi*[1] + ch*[2] + y*[3] + x*[4] (any view of a tensor is read in
+ * place).  Per pair-ray, all in float32:
+ *     xy_ray = ((x+0.5)/w, (y+0.5)/h);  direction = R(c2w_vi) * normalise(Kinv_vi * (xy_ray, 1));  origin = c2w_vi's translation
+ *     O, D = the ray in view o's camera space (w2c_o)
+ *     frame intersections with x=0, x=1, y=0, y=1 (in this order):  cc = (value - K[dim][2]) / K[dim][dim],
+ *         t = (cc*O.z - O[dim]) / (D[dim] - cc*D.z),
+ *         other = K[od][2] + K[od][od]*(O[od]*(cc*D.z - D[dim]) + D[od]*(O[dim] - cc*O.z)) / (D.z*O[dim] - D[dim]*O.z),
+ *         valid = -1e-6 <= other <= 1+1e-6  and  O.z + t*D.z > -1e-6  and  t > -1e-6
+ *     point projections at t = near_vi and t = far_vi:  q = (O + t*D) / ((O + t*D).z + FLT_EPSILON), +-inf -> +-1e8, NaN -> 0;
+ *         xy = rows 0, 1 of K*q;  valid = both in [-1e-6, 1+1e-6]  and  (O + t*D).z > -1e-6  and  t > -1e-6
+ *     lo = near's projection if valid, else the valid frame intersection of smallest t (first on ties; none valid: the first);
+ *     hi = far's projection if valid, else the valid frame intersection of largest t;   valid = lo.valid and hi.valid
+ *     xy_min, xy_max = (lo.xy, hi.xy) with every non-finite value set to 0, times valid    — an INVALID pair-ray has xy_min = xy_max = 0
+ *     for sample i < s:  pos = (i+0.5)/s;  xy_sample = xy_min + pos*(xy_max - xy_min);  xy_sample_near / _far at pos -+ 0.5/s
+ *     features[.., i, :] = valid * bilinear(images[bi, o], xy_sample), zero padding, align_corners = False: pixel coordinate
+ *         xy*(w, h) - 0.5, computed as grid_sample computes it from the grid 2*xy - 1.  Invalid pair-rays give exact zeros.
+ *     depth[.., i]: the ray of view o through xy_sample AS WRITTEN, valid or not (for an invalid pair-ray that is the point
+ *         (0, 0)); the least-squares intersection with the casting ray — the closed-form solution of intersect_rays' 3x3 normal
+ *         system; a direction dot product above 1 - 1e-5 counts as parallel and gives the point (1e10, 1e10, 1e10) —, its
+ *         distance to the origin, clipped to [near_vi, far_vi], then 1 - (1/(d+e) - 1/(far+e)) / (1/(near+e) - 1/(far+e) + e), e = 1e-10
+ * Outputs (each may be NULL: not computed): features [P,s,c]; valid [P] uint8; xy_ray [b,v,r,2]; xy_sample, xy_sample_near,
+ * xy_sample_far [P,s,2]; origins, directions [b,v,r,3]; depth [P,s]; segment [P,4] = (xy_min, xy_max), what the backward reads.
+ * Every element of a non-NULL output is written.  scratch: scratch_bytes >= ggr_epipolar_scratch_bytes(b, v, c, h, w) bytes of
+ * device memory (b*v*h*w*c floats: the feature maps laid out channel-last by a small launch of their own, so that a tap's
+ * channels are contiguous); the forward needs it only when features is not NULL.
+ * ggr_epipolar_backward: dL_dimages [b,v,c,h,w] (dense, every element written) = the scatter of dL_dfeatures [P,s,c] through the
+ * same four bilinear weights; invalid pair-rays and taps outside the image contribute nothing.  It reads `valid` and `segment`
+ * as the forward wrote them and recomputes sample points, taps and weights; cameras, images and the other outputs are not
+ * read.  The sums are float atomics into scratch (zeroed on the stream first), which a second launch transposes out: the result
+ * is reproducible up to the order of summation only, NOT to the bit.  Cameras, near and far get no gradient.
+ * Both calls allocate nothing, read nothing back, are ordered on `stream`, do not synchronise (unless `debug`) and are
+ * hipGraph-capturable; batch == 0 is valid and enqueues nothing.  GGR_E_INVALID, before anything is enqueued, for a struct_size
+ * smaller than the struct, a nonzero `reserved`, num_samples outside 1..64, channels outside 1..512, num_views outside 2..8, a
+ * negative batch, height or width below 1, a window that is empty or leaves the grid, b*v above 65535, 2^31 or more of
+ * pair-rays x samples or of map pixels (b*v*h*w) — element offsets are 64-bit, so P*s*c may exceed 2^31 —, a misaligned
+ * buffer (4 bytes), a scratch smaller than needed, or (unless batch == 0) a NULL required pointer: forward c2w, w2c, K, Kinv,
+ * near, far, and images + scratch when features is asked for; backward valid, segment, dL_dfeatures, dL_dimages, scratch. */
+typedef struct GgrEpipolarPass {
+    int32_t struct_size;            /* sizeof(GgrEpipolarPass) */
+    int32_t reserved;               /* 0 */
+    int32_t batch;                  /* b */
+    int32_t num_views;              /* v: 2..8 */
+    int32_t channels;               /* c: 1..512 */
+    int32_t height, width;          /* h, w of the feature maps */
+    int32_t num_samples;            /* s: 1..64 */
+    int32_t use_window;             /* != 0: rays only inside the window below */
+    int32_t window_y0, window_y1;   /* rows    y0 <= y < y1 of the ray grid */
+    int32_t window_x0, window_x1;   /* columns x0 <= x < x1 */
+    int32_t debug;                  /* != 0: synchronise after the launches and report their error */
+    int64_t image_strides[5];       /* of `images`, in floats: batch, view, channel, row, column */
+    const float* c2w;               /* [b,v,4,4] */
+    const float* w2c;               /* [b,v,4,4] */
+    const float* K;                 /* [b,v,3,3] */
+    const float* Kinv;              /* [b,v,3,3] */
+    const float* near;              /* [b,v] */
+    const float* far;               /* [b,v] */
+    const float* images;            /* [b,v,c,h,w] through image_strides */
+    float* features;                /* [P,s,c], or NULL */
+    uint8_t* valid;                 /* [P]: written by the forward (or NULL), read by the backward */
+    float* xy_ray;                  /* [b,v,r,2], or NULL */
+    float* xy_sample;               /* [P,s,2], or NULL */
+    float* xy_sample_near;          /* [P,s,2], or NULL */
+    float* xy_sample_far;           /* [P,s,2], or NULL */
+    float* origins;                 /* [b,v,r,3], or NULL */
+    float* directions;              /* [b,v,r,3], or NULL */
+    float* depth;                   /* [P,s], or NULL */
+    float* segment;                 /* [P,4]: written by the forward (or NULL), read by the backward */
+    const float* dL_dfeatures;      /* backward: [P,s,c] */
+    float* dL_dimages;              /* backward: [b,v,c,h,w] dense, written whole */
+    float* scratch;                 /* b*v*h*w*c floats */
+    int64_t scratch_bytes;          /* the size of `scratch` */
+} GgrEpipolarPass;
+
+/* b*v*h*w*c*4, or -1 for sizes that GgrEpipolarPass refuses */
+int64_t ggr_epipolar_scratch_bytes(int32_t batch, int32_t num_views, int32_t channels, int32_t height, int32_t width);
+int ggr_epipolar_forward(const GgrEpipolarPass* pass, void* stream);
+int ggr_epipolar_backward(const GgrEpipolarPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
