@@ -242,6 +242,17 @@ def epipolar_pass(**fields) -> GgrEpipolarPass:
     return GgrEpipolarPass(struct_size=C.sizeof(GgrEpipolarPass), **fields)
 
 
+class GgrEpipolarAttnPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("N", C.c_int32), ("S", C.c_int32), ("C", C.c_int32),
+                ("H", C.c_int32), ("qk", C.c_void_p), ("z", C.c_void_p), ("out_ctx", C.c_void_p), ("out_attn", C.c_void_p),
+                ("attn", C.c_void_p), ("dL_dctx", C.c_void_p), ("dL_dqk", C.c_void_p), ("dL_dz", C.c_void_p)]
+
+
+def epipolar_attn_pass(**fields) -> GgrEpipolarAttnPass:
+    """The argument of ggr_epipolar_attention_forward / _backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrEpipolarAttnPass(struct_size=C.sizeof(GgrEpipolarAttnPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -330,6 +341,8 @@ SYMBOLS = [
     ("ggr_epipolar_scratch_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("ggr_epipolar_forward", C.c_int, [C.POINTER(GgrEpipolarPass), C.c_void_p]),
     ("ggr_epipolar_backward", C.c_int, [C.POINTER(GgrEpipolarPass), C.c_void_p]),
+    ("ggr_epipolar_attention_forward", C.c_int, [C.POINTER(GgrEpipolarAttnPass), C.c_void_p]),
+    ("ggr_epipolar_attention_backward", C.c_int, [C.POINTER(GgrEpipolarAttnPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

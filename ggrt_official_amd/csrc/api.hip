@@ -17,6 +17,7 @@
 #include "adapter.h"
 #include "depth_head.h"
 #include "epipolar.h"
+#include "epipolar_attn.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1571,6 +1572,69 @@ int ggr_epipolar_backward(const GgrEpipolarPass* ep, void* stream) {
     ggr::launch_epipolar_backward(a, s);
     KCHECK(ep->debug != 0, s, "epipolar_backward");
     return GGR_OK;
+}
+
+// ---- the epipolar cross-attention core (epipolar_attn.hip): one query token per ray against the ray's raw samples -------------
+namespace {
+int epipolar_attn_pass_check(const GgrEpipolarAttnPass* ap, bool backward, ggr::EpiAttnArgs* a) {
+    if (!ap) return fail(GGR_E_INVALID, "null GgrEpipolarAttnPass");
+    if (ap->struct_size < (int32_t)sizeof(GgrEpipolarAttnPass))
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.struct_size %d is smaller than the %d bytes of its fields", (int)ap->struct_size,
+                    (int)sizeof(GgrEpipolarAttnPass));
+    if (ap->reserved != 0) return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.reserved must be 0, not %d", (int)ap->reserved);
+    const int N = ap->N, S = ap->S, C = ap->C, H = ap->H;
+    if (N < 0 || N > ggr::kEpiAttnMaxRays) return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.N %d is outside 0..%d", N, ggr::kEpiAttnMaxRays);
+    if (S < 1 || S > ggr::kEpiAttnMaxSamples) return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.S %d is outside 1..%d", S, ggr::kEpiAttnMaxSamples);
+    if (C < 1 || C > ggr::kEpiAttnMaxChannels) return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.C %d is outside 1..%d", C, ggr::kEpiAttnMaxChannels);
+    if (H < 1 || H > ggr::kEpiAttnMaxHeads) return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.H %d is outside 1..%d", H, ggr::kEpiAttnMaxHeads);
+    const int lds = ggr::epipolar_attn_lds_bytes(S, C);
+    if (lds > ggr::kEpiAttnLdsLimit)      // (cannot happen inside the limits above: 64 rows of 260 floats are 66 560 bytes)
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnPass: S = %d, C = %d needs %d bytes of LDS, above the %d bytes of a workgroup", S, C, lds,
+                    ggr::kEpiAttnLdsLimit);
+    if (N > 0) {
+        const void* fwd_in[] = {ap->qk, ap->z, ap->out_ctx, ap->out_attn};
+        const char* fwd_name[] = {"qk", "z", "out_ctx", "out_attn"};
+        const void* bwd_in[] = {ap->qk, ap->z, ap->attn, ap->dL_dctx, ap->dL_dqk, ap->dL_dz};
+        const char* bwd_name[] = {"qk", "z", "attn", "dL_dctx", "dL_dqk", "dL_dz"};
+        for (int i = 0; i < (backward ? 6 : 4); ++i)
+            if (!(backward ? bwd_in : fwd_in)[i])
+                return fail(GGR_E_INVALID, "GgrEpipolarAttnPass.%s is NULL", (backward ? bwd_name : fwd_name)[i]);
+    }
+    const void* all[] = {ap->qk, ap->z, ap->out_ctx, ap->out_attn, ap->attn, ap->dL_dctx, ap->dL_dqk, ap->dL_dz};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrEpipolarAttnPass: a buffer is misaligned (every float array needs 4-byte alignment)");
+    a->N = N; a->S = S; a->C = C; a->H = H;
+    a->qk = ap->qk; a->z = ap->z; a->ctx = ap->out_ctx; a->attn_out = ap->out_attn; a->attn = ap->attn; a->g_ctx = ap->dL_dctx;
+    a->g_qk = ap->dL_dqk; a->g_z = ap->dL_dz;
+    return GGR_OK;
+}
+
+int epipolar_attn_launched(hipError_t e, const ggr::EpiAttnArgs& a, const char* what) {
+    if (e != hipSuccess)
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnPass: S = %d, C = %d needs %d bytes of LDS in one workgroup, which this device refused (%s)", a.S, a.C,
+                    ggr::epipolar_attn_lds_bytes(a.S, a.C), hipGetErrorString(e));
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(GGR_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_epipolar_attention_forward(const GgrEpipolarAttnPass* ap, void* stream) {
+    g_err[0] = 0;
+    ggr::EpiAttnArgs a;
+    const int rc = epipolar_attn_pass_check(ap, false, &a);
+    if (rc) return rc;
+    if (a.N == 0) return GGR_OK;
+    return epipolar_attn_launched(ggr::launch_epipolar_attn_forward(a, (hipStream_t)stream), a, "epipolar_attention_forward");
+}
+
+int ggr_epipolar_attention_backward(const GgrEpipolarAttnPass* ap, void* stream) {
+    g_err[0] = 0;
+    ggr::EpiAttnArgs a;
+    const int rc = epipolar_attn_pass_check(ap, true, &a);
+    if (rc) return rc;
+    if (a.N == 0) return GGR_OK;
+    return epipolar_attn_launched(ggr::launch_epipolar_attn_backward(a, (hipStream_t)stream), a, "epipolar_attention_backward");
 }
 
 // ---- the distortion pass (blend_dist.hip): the depth-distortion plane over a forward's lists, and its backward -----------------

@@ -506,6 +506,95 @@ def fused_epipolar_sampler(images: Tensor, extrinsics: Tensor, intrinsics: Tenso
                            xy_sample_far=out[5], origins=out[6], directions=out[7], depth=out[8])
 
 
+class _EpipolarAttentionCore(torch.autograd.Function):
+    """ggr_epipolar_attention_forward / _backward (csrc/epipolar_attn.hip) behind autograd: qk [N,H,C], z [N,S,C], float32 and
+    contiguous on arrival → ctx [N,H,C], attn [N,H,S].  attn is the only tensor saved beside the inputs."""
+
+    @staticmethod
+    def _call(name, dev, dims, **pointers):
+        n, s, c, h = dims
+        ap = _lib.epipolar_attn_pass(reserved=0, N=n, S=s, C=c, H=h, **pointers)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.load(), name)(C.byref(ap), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+    @staticmethod
+    def forward(ctx, qk, z):
+        dev = z.device
+        (n, h, c), s = qk.shape, z.shape[1]
+        out = torch.empty((n, h, c), dtype=torch.float32, device=dev)
+        attn = torch.empty((n, h, s), dtype=torch.float32, device=dev)
+        _EpipolarAttentionCore._call("ggr_epipolar_attention_forward", dev, (n, s, c, h), qk=qk.data_ptr(), z=z.data_ptr(),
+                                     out_ctx=out.data_ptr(), out_attn=attn.data_ptr())
+        ctx.save_for_backward(qk, z, attn)
+        ctx.mark_non_differentiable(attn)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, g_out, _g_attn):
+        qk, z, attn = ctx.saved_tensors
+        dev = z.device
+        (n, h, c), s = qk.shape, z.shape[1]
+        g_out = g_out.to(dtype=torch.float32).contiguous()
+        g_qk, g_z = torch.empty_like(qk), torch.empty_like(z)
+        _EpipolarAttentionCore._call("ggr_epipolar_attention_backward", dev, (n, s, c, h), qk=qk.data_ptr(), z=z.data_ptr(),
+                                     attn=attn.data_ptr(), dL_dctx=g_out.data_ptr(), dL_dqk=g_qk.data_ptr(), dL_dz=g_z.data_ptr())
+        return g_qk, g_z
+
+
+def epipolar_attention_core(qk: Tensor, z: Tensor):
+    """The per-ray part of GGRt's epipolar cross-attention as one HIP launch, and one more for the backward (INTEGRATION.md §25;
+    the arithmetic: ``GgrEpipolarAttnPass`` in include/ggr_raster.h).  ``qk`` [N,H,C] is the query with the key projection folded
+    in, ``z`` [N,S,C] the ray's raw samples.  Returns ``(ctx, attn)``: ``ctx[n,h] = Σ_s attn[n,h,s]·z[n,s]`` [N,H,C],
+    differentiable with respect to both inputs, and ``attn = softmax_s(qk·z)`` [N,H,S], detached (for visualisation).  Two runs
+    give the same bits, forward and backward."""
+    if qk.device.type != "cuda" or z.device.type != "cuda":
+        raise RuntimeError("epipolar_attention_core runs on the GPU only (there is no CPU fallback)")
+    if qk.dim() != 3 or z.dim() != 3 or qk.shape[0] != z.shape[0] or qk.shape[2] != z.shape[2]:
+        raise ValueError(f"qk {tuple(qk.shape)} is not [N, H, C] for z {tuple(z.shape)} = [N, S, C]")
+    f = lambda t: t.to(device=z.device, dtype=torch.float32).contiguous()
+    return _EpipolarAttentionCore.apply(f(qk), f(z))
+
+
+def fused_epipolar_attention(x: Tensor, z: Tensor, w_q: Tensor, w_kv: Tensor, w_out: Optional[Tensor], b_out: Optional[Tensor],
+                             heads: int, return_weights: bool = False):
+    """GGRt's ``Attention.forward(x, z)`` (``transformer/attention.py:57-74``) where ``EpipolarTransformer.forward`` calls it: ONE
+    query token per ray against the ray's S samples, without the key and value tensors.  ``x`` [N,dim] or
+    [N,1,dim] (after the caller's LayerNorm), ``z`` [N,S,kv_dim] (not normed), ``w_q`` = ``to_q.weight`` [H·D,dim], ``w_kv`` =
+    ``to_kv.weight`` [2·H·D,kv_dim], ``w_out`` / ``b_out`` = ``to_out[0]``'s weight [dim,H·D] and bias, or ``None`` for the
+    reference's ``project_out = False`` (heads = 1, D = dim).  ``to_q``, the fold ``qk = scale·Wk_hᵀq_h``, ``Wv_h·ctx_h`` and
+    ``to_out`` are [N,·]-sized torch GEMMs; the logits, the softmax over the samples and the weighted sum are
+    ``epipolar_attention_core``.  Autograd gives every gradient (x, z and the weights).  Returns the result in ``x``'s shape — with
+    ``return_weights`` also the attention weights [N,H,S], detached.  Dropout is not modelled (GGRt's is 0.0)."""
+    if x.dim() == 3 and x.shape[1] != 1:
+        raise ValueError(f"fused_epipolar_attention takes ONE query token per ray: x {tuple(x.shape)} has {x.shape[1]} "
+                         "(more than one query token per ray is not implemented)")
+    if x.device.type != "cuda" or z.device.type != "cuda":
+        raise RuntimeError("fused_epipolar_attention runs on the GPU only (there is no CPU fallback)")
+    if x.dim() not in (2, 3) or z.dim() != 3 or z.shape[0] != x.shape[0]:
+        raise ValueError(f"x {tuple(x.shape)} is not [N, dim] or [N, 1, dim] for z {tuple(z.shape)} = [N, S, kv_dim]")
+    heads = int(heads)
+    n, dim, kv_dim = x.shape[0], x.shape[-1], z.shape[2]
+    inner = w_q.shape[0]
+    if heads < 1 or inner % heads != 0 or tuple(w_q.shape) != (inner, dim) or tuple(w_kv.shape) != (2 * inner, kv_dim):
+        raise ValueError(f"w_q {tuple(w_q.shape)} must be [H*D, {dim}] and w_kv {tuple(w_kv.shape)} [2*H*D, {kv_dim}] with H = {heads}")
+    if w_out is None and inner != dim:
+        raise ValueError(f"without w_out the result is the heads' output itself: H*D = {inner} must equal dim = {dim}")
+    d = inner // heads
+    f32 = lambda t: t.to(dtype=torch.float32)
+    q = (f32(x).reshape(n, dim) @ f32(w_q).t()).reshape(n, heads, d)
+    wk, wv = f32(w_kv)[:inner].reshape(heads, d, kv_dim), f32(w_kv)[inner:].reshape(heads, d, kv_dim)
+    qk = torch.einsum("nhd,hdc->nhc", q, wk * (d ** -0.5))      # (the scale on the [H,D,C] weights: no [N,H,C] temporary)
+    ctx, attn = epipolar_attention_core(qk, z)
+    del qk, q
+    out = torch.einsum("nhc,hdc->nhd", ctx, wv).reshape(n, inner)
+    if w_out is not None:
+        out = torch.nn.functional.linear(out, f32(w_out), None if b_out is None else f32(b_out))
+    out = out.reshape(x.shape)
+    return (out, attn) if return_weights else out
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

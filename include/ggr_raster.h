@@ -1038,6 +1038,52 @@ int64_t ggr_epipolar_scratch_bytes(int32_t batch, int32_t num_views, int32_t cha
 int ggr_epipolar_forward(const GgrEpipolarPass* pass, void* stream);
 int ggr_epipolar_backward(const GgrEpipolarPass* pass, void* stream);
 
+/* The core of GGRt's epipolar cross-attention (encoder/epipolar/epipolar_transformer.py:156-165 calling
+ * transformer/attention.py:57-74 with ONE query token per ray and the ray's s samples as keys and values), without the key and
+ * value tensors.  With Wk_h, Wv_h head h's [D, C] blocks of to_kv.weight and q_h head h's slice of to_q(x):
+ *     logit[h,s] = scale * q_h . (Wk_h z_s) = (scale * Wk_h^T q_h) . z_s = qk_h . z_s
+ *     out_h      = sum_s a[h,s] * (Wv_h z_s) = Wv_h * (sum_s a[h,s] z_s)   = Wv_h * ctx_h
+ * so both projections are the caller's, over N rays instead of N*S samples; this pass is what remains per ray, on the raw z.
+ * Sizes: N rays (0..2^25), S samples (1..64), C channels of z (1..256), H heads (1..8).  All buffers are device memory, float32,
+ * dense and 4-byte aligned (z is read with 16-byte loads when it is 16-byte aligned and C is a multiple of 4).
+ * ggr_epipolar_attention_forward: qk [N,H,C], z [N,S,C] ->
+ *     logit[n,h,s] = sum_c qk[n,h,c] * z[n,s,c]                                (fused multiply-adds, c ascending)
+ *     out_attn[n,h,s] = exp(logit[n,h,s] - max_s' logit[n,h,s']) / sum_s' exp(logit[n,h,s'] - max)
+ *     out_ctx[n,h,c] = sum_s out_attn[n,h,s] * z[n,s,c]                        (s ascending)
+ * out_attn [N,H,S] is the only state the backward needs beside the inputs.
+ * ggr_epipolar_attention_backward: qk, z, attn [N,H,S] (the forward's out_attn), dL_dctx [N,H,C] ->
+ *     da[h,s]  = sum_c dL_dctx[h,c] * z[s,c]
+ *     dl[h,s]  = attn[h,s] * (da[h,s] - sum_s' attn[h,s'] * da[h,s'])
+ *     dL_dqk[n,h,c] = sum_s dl[h,s] * z[s,c]
+ *     dL_dz[n,s,c]  = sum_h (attn[h,s] * dL_dctx[h,c] + dl[h,s] * qk[h,c])
+ * Every element of out_ctx, out_attn, dL_dqk and dL_dz is written, once, by the one wave that owns ray n, in a fixed order of
+ * summation: no atomics, and two calls on the same inputs give the same bits.  z is read from memory once per call.
+ * Both calls allocate nothing, read nothing back, are ordered on `stream`, do not synchronise and are hipGraph-capturable;
+ * N == 0 is valid, enqueues nothing and follows no pointer.  GGR_E_INVALID, before anything is enqueued, for a struct_size
+ * smaller than the struct, a nonzero `reserved`, N outside 0..2^25, S outside 1..64, C outside 1..256, H outside 1..8, a
+ * misaligned buffer, a ray tile (S rows of 4*((ceil(C/4))|1) floats: 66 560 bytes at the most) that the device does not
+ * grant one workgroup as LDS, or (unless N == 0) a NULL required pointer: forward qk, z, out_ctx, out_attn; backward qk, z,
+ * attn, dL_dctx, dL_dqk, dL_dz.  Element offsets are 64-bit: N*S*C may exceed 2^31. */
+typedef struct GgrEpipolarAttnPass {
+    int32_t struct_size;            /* sizeof(GgrEpipolarAttnPass) */
+    int32_t reserved;               /* 0 */
+    int32_t N;                      /* rays: 0..2^25 */
+    int32_t S;                      /* samples per ray: 1..64 */
+    int32_t C;                      /* channels of z: 1..256 */
+    int32_t H;                      /* heads: 1..8 */
+    const float* qk;                /* [N,H,C]: scale * Wk_h^T q_h */
+    const float* z;                 /* [N,S,C] */
+    float* out_ctx;                 /* forward: [N,H,C] */
+    float* out_attn;                /* forward: [N,H,S] */
+    const float* attn;              /* backward: [N,H,S], the forward's out_attn */
+    const float* dL_dctx;           /* backward: [N,H,C] */
+    float* dL_dqk;                  /* backward: [N,H,C], written whole */
+    float* dL_dz;                   /* backward: [N,S,C], written whole */
+} GgrEpipolarAttnPass;
+
+int ggr_epipolar_attention_forward(const GgrEpipolarAttnPass* pass, void* stream);
+int ggr_epipolar_attention_backward(const GgrEpipolarAttnPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
