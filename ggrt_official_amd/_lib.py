@@ -253,6 +253,19 @@ def epipolar_attn_pass(**fields) -> GgrEpipolarAttnPass:
     return GgrEpipolarAttnPass(struct_size=C.sizeof(GgrEpipolarAttnPass), **fields)
 
 
+class GgrEpipolarAttnEncPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("N", C.c_int32), ("S", C.c_int32), ("C", C.c_int32),
+                ("H", C.c_int32), ("num_octaves", C.c_int32), ("reserved2", C.c_int32), ("qk", C.c_void_p), ("qe", C.c_void_p),
+                ("features", C.c_void_p), ("depth", C.c_void_p), ("out_ctx_f", C.c_void_p), ("out_ctx_e", C.c_void_p),
+                ("out_attn", C.c_void_p), ("attn", C.c_void_p), ("dL_dctx_f", C.c_void_p), ("dL_dctx_e", C.c_void_p),
+                ("dL_dqk", C.c_void_p), ("dL_dqe", C.c_void_p), ("dL_dfeatures", C.c_void_p), ("dL_ddepth", C.c_void_p)]
+
+
+def epipolar_attn_enc_pass(**fields) -> GgrEpipolarAttnEncPass:
+    """The argument of ggr_epipolar_attention_encoded_forward / _backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrEpipolarAttnEncPass(struct_size=C.sizeof(GgrEpipolarAttnEncPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -343,6 +356,8 @@ SYMBOLS = [
     ("ggr_epipolar_backward", C.c_int, [C.POINTER(GgrEpipolarPass), C.c_void_p]),
     ("ggr_epipolar_attention_forward", C.c_int, [C.POINTER(GgrEpipolarAttnPass), C.c_void_p]),
     ("ggr_epipolar_attention_backward", C.c_int, [C.POINTER(GgrEpipolarAttnPass), C.c_void_p]),
+    ("ggr_epipolar_attention_encoded_forward", C.c_int, [C.POINTER(GgrEpipolarAttnEncPass), C.c_void_p]),
+    ("ggr_epipolar_attention_encoded_backward", C.c_int, [C.POINTER(GgrEpipolarAttnEncPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

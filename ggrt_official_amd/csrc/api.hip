@@ -18,6 +18,7 @@
 #include "depth_head.h"
 #include "epipolar.h"
 #include "epipolar_attn.h"
+#include "epipolar_attn_enc.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1635,6 +1636,75 @@ int ggr_epipolar_attention_backward(const GgrEpipolarAttnPass* ap, void* stream)
     if (rc) return rc;
     if (a.N == 0) return GGR_OK;
     return epipolar_attn_launched(ggr::launch_epipolar_attn_backward(a, (hipStream_t)stream), a, "epipolar_attention_backward");
+}
+
+// ---- the same core with the depth encoding folded in (epipolar_attn_enc.hip): the sampler's raw features and depth, no z ------
+namespace {
+int epipolar_attn_enc_pass_check(const GgrEpipolarAttnEncPass* ap, bool backward, ggr::EpiAttnEncArgs* a) {
+    if (!ap) return fail(GGR_E_INVALID, "null GgrEpipolarAttnEncPass");
+    if (ap->struct_size < (int32_t)sizeof(GgrEpipolarAttnEncPass))
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.struct_size %d is smaller than the %d bytes of its fields", (int)ap->struct_size,
+                    (int)sizeof(GgrEpipolarAttnEncPass));
+    if (ap->reserved != 0 || ap->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.reserved must be 0, not %d / %d", (int)ap->reserved, (int)ap->reserved2);
+    const int N = ap->N, S = ap->S, C = ap->C, H = ap->H, O = ap->num_octaves;
+    if (N < 0 || N > ggr::kEpiAttnMaxRays) return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.N %d is outside 0..%d", N, ggr::kEpiAttnMaxRays);
+    if (S < 1 || S > ggr::kEpiAttnMaxSamples) return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.S %d is outside 1..%d", S, ggr::kEpiAttnMaxSamples);
+    if (C < 1 || C > ggr::kEpiAttnMaxChannels) return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.C %d is outside 1..%d", C, ggr::kEpiAttnMaxChannels);
+    if (H < 1 || H > ggr::kEpiAttnMaxHeads) return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.H %d is outside 1..%d", H, ggr::kEpiAttnMaxHeads);
+    if (O < 1 || O > ggr::kEpiAttnEncMaxOctaves)
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.num_octaves %d is outside 1..%d (without an encoding the pass to call is GgrEpipolarAttnPass)", O,
+                    ggr::kEpiAttnEncMaxOctaves);
+    const int lds = ggr::epipolar_attn_enc_lds_bytes(S, C, O);
+    if (lds > ggr::kEpiAttnLdsLimit)      // (cannot happen inside the limits above: 64 rows of 292 floats are 74 752 bytes)
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass: S = %d, C = %d, num_octaves = %d needs %d bytes of LDS, above the %d bytes of a workgroup", S, C,
+                    O, lds, ggr::kEpiAttnLdsLimit);
+    if (N > 0) {
+        const void* fwd_in[] = {ap->qk, ap->qe, ap->features, ap->depth, ap->out_ctx_f, ap->out_ctx_e, ap->out_attn};
+        const char* fwd_name[] = {"qk", "qe", "features", "depth", "out_ctx_f", "out_ctx_e", "out_attn"};
+        const void* bwd_in[] = {ap->qk, ap->qe, ap->features, ap->depth, ap->attn, ap->dL_dctx_f, ap->dL_dctx_e, ap->dL_dqk, ap->dL_dqe, ap->dL_dfeatures};
+        const char* bwd_name[] = {"qk", "qe", "features", "depth", "attn", "dL_dctx_f", "dL_dctx_e", "dL_dqk", "dL_dqe", "dL_dfeatures"};
+        for (int i = 0; i < (backward ? 10 : 7); ++i)
+            if (!(backward ? bwd_in : fwd_in)[i])
+                return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass.%s is NULL", (backward ? bwd_name : fwd_name)[i]);
+    }
+    const void* all[] = {ap->qk, ap->qe, ap->features, ap->depth, ap->out_ctx_f, ap->out_ctx_e, ap->out_attn, ap->attn, ap->dL_dctx_f, ap->dL_dctx_e,
+                         ap->dL_dqk, ap->dL_dqe, ap->dL_dfeatures, ap->dL_ddepth};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass: a buffer is misaligned (every float array needs 4-byte alignment)");
+    a->N = N; a->S = S; a->C = C; a->H = H; a->O = O;
+    a->qk = ap->qk; a->qe = ap->qe; a->f = ap->features; a->d = ap->depth; a->ctx_f = ap->out_ctx_f; a->ctx_e = ap->out_ctx_e; a->attn_out = ap->out_attn;
+    a->attn = ap->attn; a->g_f_ctx = ap->dL_dctx_f; a->g_e_ctx = ap->dL_dctx_e; a->g_qk = ap->dL_dqk; a->g_qe = ap->dL_dqe; a->g_f = ap->dL_dfeatures;
+    a->g_d = ap->dL_ddepth;
+    return GGR_OK;
+}
+
+int epipolar_attn_enc_launched(hipError_t e, const ggr::EpiAttnEncArgs& a, const char* what) {
+    if (e != hipSuccess)
+        return fail(GGR_E_INVALID, "GgrEpipolarAttnEncPass: S = %d, C = %d, num_octaves = %d needs %d bytes of LDS in one workgroup, which this device refused (%s)",
+                    a.S, a.C, a.O, ggr::epipolar_attn_enc_lds_bytes(a.S, a.C, a.O), hipGetErrorString(e));
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(GGR_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_epipolar_attention_encoded_forward(const GgrEpipolarAttnEncPass* ap, void* stream) {
+    g_err[0] = 0;
+    ggr::EpiAttnEncArgs a;
+    const int rc = epipolar_attn_enc_pass_check(ap, false, &a);
+    if (rc) return rc;
+    if (a.N == 0) return GGR_OK;
+    return epipolar_attn_enc_launched(ggr::launch_epipolar_attn_enc_forward(a, (hipStream_t)stream), a, "epipolar_attention_encoded_forward");
+}
+
+int ggr_epipolar_attention_encoded_backward(const GgrEpipolarAttnEncPass* ap, void* stream) {
+    g_err[0] = 0;
+    ggr::EpiAttnEncArgs a;
+    const int rc = epipolar_attn_enc_pass_check(ap, true, &a);
+    if (rc) return rc;
+    if (a.N == 0) return GGR_OK;
+    return epipolar_attn_enc_launched(ggr::launch_epipolar_attn_enc_backward(a, (hipStream_t)stream), a, "epipolar_attention_encoded_backward");
 }
 
 // ---- the distortion pass (blend_dist.hip): the depth-distortion plane over a forward's lists, and its backward -----------------

@@ -595,6 +595,153 @@ def fused_epipolar_attention(x: Tensor, z: Tensor, w_q: Tensor, w_kv: Tensor, w_
     return (out, attn) if return_weights else out
 
 
+def _enc_attn_call(name, dev, dims, **pointers):
+    n, s, c, h, o = dims
+    ap = _lib.epipolar_attn_enc_pass(reserved=0, N=n, S=s, C=c, H=h, num_octaves=o, reserved2=0, **pointers)
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), name)(C.byref(ap), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+
+def _enc_attn_forward(qk, qe, features, depth):
+    """ggr_epipolar_attention_encoded_forward on float32, contiguous tensors → ctx_f [N,H,C], ctx_e [N,H,E], attn [N,H,S]"""
+    dev = features.device
+    (n, h, c), s, e = qk.shape, features.shape[1], qe.shape[2]
+    out_f = torch.empty((n, h, c), dtype=torch.float32, device=dev)
+    out_e = torch.empty((n, h, e), dtype=torch.float32, device=dev)
+    attn = torch.empty((n, h, s), dtype=torch.float32, device=dev)
+    _enc_attn_call("ggr_epipolar_attention_encoded_forward", dev, (n, s, c, h, e // 2), qk=qk.data_ptr(), qe=qe.data_ptr(),
+                   features=features.data_ptr(), depth=depth.data_ptr(), out_ctx_f=out_f.data_ptr(), out_ctx_e=out_e.data_ptr(),
+                   out_attn=attn.data_ptr())
+    return out_f, out_e, attn
+
+
+def _enc_attn_backward(qk, qe, features, depth, attn, g_f, g_e, depth_grad):
+    """ggr_epipolar_attention_encoded_backward → g_qk, g_qe, g_features, g_depth (None unless `depth_grad`)"""
+    dev = features.device
+    (n, h, c), s, e = qk.shape, features.shape[1], qe.shape[2]
+    g_f, g_e = g_f.to(dtype=torch.float32).contiguous(), g_e.to(dtype=torch.float32).contiguous()
+    g_qk, g_qe, g_feat = torch.empty_like(qk), torch.empty_like(qe), torch.empty_like(features)
+    g_d = torch.empty_like(depth) if depth_grad else None
+    _enc_attn_call("ggr_epipolar_attention_encoded_backward", dev, (n, s, c, h, e // 2), qk=qk.data_ptr(), qe=qe.data_ptr(),
+                   features=features.data_ptr(), depth=depth.data_ptr(), attn=attn.data_ptr(), dL_dctx_f=g_f.data_ptr(),
+                   dL_dctx_e=g_e.data_ptr(), dL_dqk=g_qk.data_ptr(), dL_dqe=g_qe.data_ptr(), dL_dfeatures=g_feat.data_ptr(),
+                   dL_ddepth=None if g_d is None else g_d.data_ptr())
+    return g_qk, g_qe, g_feat, g_d
+
+
+class _EpipolarEncodedAttentionCore(torch.autograd.Function):
+    """ggr_epipolar_attention_encoded_forward / _backward (csrc/epipolar_attn_enc.hip) behind autograd: qk [N,H,C], qe [N,H,E],
+    features [N,S,C], depth [N,S], float32 and contiguous on arrival → ctx_f [N,H,C], ctx_e [N,H,E], attn [N,H,S].  attn is the
+    only tensor saved beside the inputs; dL/ddepth is computed only when depth asks for it."""
+
+    @staticmethod
+    def forward(ctx, qk, qe, features, depth):
+        out_f, out_e, attn = _enc_attn_forward(qk, qe, features, depth)
+        ctx.save_for_backward(qk, qe, features, depth, attn)
+        ctx.mark_non_differentiable(attn)
+        return out_f, out_e, attn
+
+    @staticmethod
+    def backward(ctx, g_f, g_e, _g_attn):
+        return _enc_attn_backward(*ctx.saved_tensors, g_f, g_e, ctx.needs_input_grad[3])
+
+
+class _EpipolarEncodedAttentionFolded(torch.autograd.Function):
+    """The same with ``qe = qk @ w_enc`` inside: qk [N,H,C], w_enc [C,E], features, depth → ctx_f, ctx_e, attn.  The fold's
+    backward adds ``g_qe @ w_encᵀ`` into the kernel's dL/dqk IN PLACE: left to autograd, the fold keeps qk, a second [N,H,C]
+    gradient and their sum alive beside dL/dfeatures, at the peak of the whole step.  qe [N,H,E] is computed again in the
+    backward instead of being saved."""
+
+    @staticmethod
+    def forward(ctx, qk, w_enc, features, depth):
+        out_f, out_e, attn = _enc_attn_forward(qk, qk @ w_enc, features, depth)
+        ctx.save_for_backward(qk, w_enc, features, depth, attn)
+        ctx.mark_non_differentiable(attn)
+        return out_f, out_e, attn
+
+    @staticmethod
+    def backward(ctx, g_f, g_e, _g_attn):
+        qk, w_enc, features, depth, attn = ctx.saved_tensors
+        g_qk, g_qe, g_feat, g_d = _enc_attn_backward(qk, qk @ w_enc, features, depth, attn, g_f, g_e, ctx.needs_input_grad[3])
+        c, e = w_enc.shape
+        g_w = qk.reshape(-1, c).t() @ g_qe.reshape(-1, e)
+        g_qk.view(-1, c).addmm_(g_qe.view(-1, e), w_enc.t())
+        return g_qk, g_w, g_feat, g_d
+
+
+def epipolar_encoded_attention_core(qk: Tensor, qe: Tensor, features: Tensor, depth: Tensor):
+    """``epipolar_attention_core`` on ``z = features + linear(PE(depth))`` without z, as one HIP launch, and one more for the
+    backward (the arithmetic and the encoding's exact contract: ``GgrEpipolarAttnEncPass`` in
+    include/ggr_raster.h).  ``qk`` [N,H,C] is the query with the key projection folded in, ``qe`` [N,H,2·O] = ``qk @ w_enc`` that
+    query against the encoding's ``nn.Linear``, ``features`` [N,S,C] and ``depth`` [N,S] the sampler's.  Returns
+    ``(ctx_f, ctx_e, attn)``: ``ctx_f[n,h] = Σ_s attn[n,h,s]·features[n,s]`` [N,H,C] and ``ctx_e[n,h] = Σ_s attn[n,h,s]·PE(depth[n,s])``
+    [N,H,2·O], differentiable with respect to all four inputs (``depth`` only if it requires a gradient), and ``attn`` [N,H,S],
+    detached.  The number of octaves O is ``qe.shape[-1] // 2``, 1..16.  Two runs give the same bits, forward and backward."""
+    if any(t.device.type != "cuda" for t in (qk, qe, features, depth)):
+        raise RuntimeError("epipolar_encoded_attention_core runs on the GPU only (there is no CPU fallback)")
+    if qk.dim() != 3 or features.dim() != 3 or qk.shape[0] != features.shape[0] or qk.shape[2] != features.shape[2]:
+        raise ValueError(f"qk {tuple(qk.shape)} is not [N, H, C] for features {tuple(features.shape)} = [N, S, C]")
+    if qe.dim() != 3 or tuple(qe.shape[:2]) != tuple(qk.shape[:2]):
+        raise ValueError(f"qe {tuple(qe.shape)} is not [N, H, 2*num_octaves] for qk {tuple(qk.shape)} = [N, H, C]")
+    if qe.shape[2] % 2 != 0:
+        raise ValueError(f"qe {tuple(qe.shape)}: the last dimension is 2*num_octaves (a sine and a cosine per octave), not the odd {qe.shape[2]}")
+    if tuple(depth.shape) != tuple(features.shape[:2]):
+        raise ValueError(f"depth {tuple(depth.shape)} is not [N, S] for features {tuple(features.shape)} = [N, S, C]")
+    f = lambda t: t.to(device=features.device, dtype=torch.float32).contiguous()
+    return _EpipolarEncodedAttentionCore.apply(f(qk), f(qe), f(features), f(depth))
+
+
+def fused_epipolar_encoded_attention(x: Tensor, features: Tensor, depth: Tensor, w_enc: Tensor, b_enc: Optional[Tensor], w_q: Tensor,
+                                     w_kv: Tensor, w_out: Optional[Tensor], b_out: Optional[Tensor], heads: int,
+                                     return_weights: bool = False):
+    """``fused_epipolar_attention(x, features + linear(PE(depth[..., None]), w_enc, b_enc), w_q, w_kv, w_out, b_out, heads)`` in
+    value and in every gradient, without that z: GGRt's ``EpipolarTransformer.forward`` lines 120-121 and 157-160 on the sampler's
+    own outputs.  ``features`` [N,S,C] and ``depth`` [N,S] are ``EpipolarSamples.features`` / ``.depth``
+    reshaped, ``w_enc`` [C,2·O] and ``b_enc`` [C] (or None) the weight and bias of ``depth_encoding[1]``, PE the reference's
+    ``PositionalEncoding(O)`` on its float32 constants; the rest as ``fused_epipolar_attention``.  The ``nn.Linear`` of the
+    encoding turns into ``qe = qk @ w_enc`` before and ``(Wv_h·w_enc)·ctx_e_h + Wv_h·b_enc`` after the kernels of
+    ``epipolar_encoded_attention_core``: [N·H,·]-sized GEMMs instead of one over N·S tokens.  Autograd gives every gradient (x, features, depth if it requires one,
+    w_enc, b_enc and the attention's weights)."""
+    if x.dim() == 3 and x.shape[1] != 1:
+        raise ValueError(f"fused_epipolar_encoded_attention takes ONE query token per ray: x {tuple(x.shape)} has {x.shape[1]} "
+                         "(more than one query token per ray is not implemented)")
+    if x.device.type != "cuda" or features.device.type != "cuda" or depth.device.type != "cuda":
+        raise RuntimeError("fused_epipolar_encoded_attention runs on the GPU only (there is no CPU fallback)")
+    if x.dim() not in (2, 3) or features.dim() != 3 or features.shape[0] != x.shape[0]:
+        raise ValueError(f"x {tuple(x.shape)} is not [N, dim] or [N, 1, dim] for features {tuple(features.shape)} = [N, S, kv_dim]")
+    if tuple(depth.shape) != tuple(features.shape[:2]):
+        raise ValueError(f"depth {tuple(depth.shape)} is not [N, S] for features {tuple(features.shape)} = [N, S, kv_dim]")
+    heads = int(heads)
+    n, dim, kv_dim = x.shape[0], x.shape[-1], features.shape[2]
+    inner = w_q.shape[0]
+    if w_enc.dim() != 2 or w_enc.shape[0] != kv_dim or w_enc.shape[1] % 2 != 0 or (b_enc is not None and tuple(b_enc.shape) != (kv_dim,)):
+        raise ValueError(f"w_enc {tuple(w_enc.shape)} must be [{kv_dim}, 2*num_octaves] and b_enc [{kv_dim}] or None")
+    if heads < 1 or inner % heads != 0 or tuple(w_q.shape) != (inner, dim) or tuple(w_kv.shape) != (2 * inner, kv_dim):
+        raise ValueError(f"w_q {tuple(w_q.shape)} must be [H*D, {dim}] and w_kv {tuple(w_kv.shape)} [2*H*D, {kv_dim}] with H = {heads}")
+    if w_out is None and inner != dim:
+        raise ValueError(f"without w_out the result is the heads' output itself: H*D = {inner} must equal dim = {dim}")
+    d = inner // heads
+    f32 = lambda t: t.to(dtype=torch.float32)
+    q = (f32(x).reshape(n, dim) @ f32(w_q).t()).reshape(n, heads, d)
+    wk, wv = f32(w_kv)[:inner].reshape(heads, d, kv_dim), f32(w_kv)[inner:].reshape(heads, d, kv_dim)
+    qk = torch.einsum("nhd,hdc->nhc", q, wk * (d ** -0.5))
+    cont = lambda t: f32(t).contiguous()
+    # qe = qk @ w_enc [N,H,E], the encoding's Linear on the query's side, is folded inside (and its backward adds into dL/dqk in place)
+    ctx_f, ctx_e, attn = _EpipolarEncodedAttentionFolded.apply(qk.contiguous(), cont(w_enc), cont(features), cont(depth))
+    del qk, q
+    out = torch.einsum("nhc,hdc->nhd", ctx_f, wv)
+    out = out + torch.einsum("nhe,hde->nhd", ctx_e, wv @ f32(w_enc))     # Wv_h·w_enc [H,D,E]: no [N,H,C] temporary
+    if b_enc is not None:
+        out = out + wv @ f32(b_enc)                                # Wv_h·b_enc [H,D]
+    out = out.reshape(n, inner)
+    if w_out is not None:
+        out = torch.nn.functional.linear(out, f32(w_out), None if b_out is None else f32(b_out))
+    out = out.reshape(x.shape)
+    return (out, attn) if return_weights else out
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

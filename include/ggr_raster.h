@@ -1084,6 +1084,68 @@ typedef struct GgrEpipolarAttnPass {
 int ggr_epipolar_attention_forward(const GgrEpipolarAttnPass* pass, void* stream);
 int ggr_epipolar_attention_backward(const GgrEpipolarAttnPass* pass, void* stream);
 
+/* The same core with GGRt's depth encoding folded in (encoder/epipolar/epipolar_transformer.py:120-121: the keys and values are
+ * z_s = f_s + W pe(d_s) + b, with f the sampled features, d the samples' relative disparity, pe the reference's
+ * PositionalEncoding(num_octaves) and (W [C,E], b [C]) the nn.Linear behind it), without z.  E = 2*num_octaves and
+ *     pe[2k+p](d) = sin(F * 2^k * d + p * P),   k = 0..num_octaves-1, p = 0, 1
+ * with F = 6.2831854820251465 (float32(2 pi), bits 0x40C90FDB) and P = 1.5707963705062866 (float32(pi/2), bits 0x3FC90FDB) taken as
+ * REAL numbers: the reference's module on its own float32 buffers in exact arithmetic (not sin(2 pi 2^k d): F - 2 pi = 1.7485e-7
+ * shows at the high octaves).  Then
+ *     logit[h,s] = qk_h . z_s = qk_h . f_s + (W^T qk_h) . pe(d_s) + qk_h . b        (the last term is the same for every s)
+ *     ctx_h      = sum_s a[h,s] z_s = sum_s a[h,s] f_s + W (sum_s a[h,s] pe(d_s)) + b
+ * so the caller folds qe = qk W [N,H,E] before and W ctx_e + b after, both over N*H rows; this pass is what remains per ray, on
+ * the sampler's raw features and depth.  Sizes and buffers as GgrEpipolarAttnPass, and num_octaves 1..16.
+ * ggr_epipolar_attention_encoded_forward: qk [N,H,C], qe [N,H,E], features [N,S,C], depth [N,S] ->
+ *     logit[n,h,s] = sum_c qk[n,h,c] * f[n,s,c] + sum_j qe[n,h,j] * pe_j(d[n,s])     (fused multiply-adds, c then j ascending)
+ *     out_attn[n,h,s] = exp(logit[n,h,s] - max_s' logit[n,h,s']) / sum_s' exp(logit[n,h,s'] - max)
+ *     out_ctx_f[n,h,c] = sum_s out_attn[n,h,s] * f[n,s,c]     out_ctx_e[n,h,j] = sum_s out_attn[n,h,s] * pe_j(d[n,s])   (s ascending)
+ * ggr_epipolar_attention_encoded_backward: the same inputs, attn [N,H,S] (the forward's out_attn), dL_dctx_f [N,H,C], dL_dctx_e [N,H,E] ->
+ *     da[h,s]  = sum_c dL_dctx_f[h,c] * f[s,c] + sum_j dL_dctx_e[h,j] * pe_j(d[s])
+ *     dl[h,s]  = attn[h,s] * (da[h,s] - sum_s' attn[h,s'] * da[h,s'])
+ *     dL_dqk[n,h,c] = sum_s dl[h,s] * f[s,c]                  dL_dqe[n,h,j] = sum_s dl[h,s] * pe_j(d[s])
+ *     dL_dfeatures[n,s,c] = sum_h (attn[h,s] * dL_dctx_f[h,c] + dl[h,s] * qk[h,c])
+ *     dL_ddepth[n,s] = sum_k sum_p (sum_h attn[h,s] * dL_dctx_e[h,2k+p] + dl[h,s] * qe[h,2k+p]) * F * 2^k * cos(F * 2^k * d[s] + p * P)
+ * dL_ddepth is optional: NULL skips it.  The sines are evaluated on an exactly reduced argument (2^k d less its nearest integer,
+ * times F, plus (F - 2 pi) times that integer): for d in [0, 1] they are within 1e-6 of the contract at every octave, where the
+ * reference's float32 module is off by 1.3e-4 at octave 10; the error grows with 1.75e-7 * 2^k * |d| * 2^-24 beyond that range.
+ * Every element of every output is written, once, by the one wave that owns ray n, in a fixed order of summation: no atomics,
+ * and two calls on the same inputs give the same bits.  features and depth are read from memory once per call; z never exists.
+ * Both calls allocate nothing, read nothing back, are ordered on `stream`, do not synchronise and are hipGraph-capturable;
+ * N == 0 is valid, enqueues nothing and follows no pointer.  GGR_E_INVALID, before anything is enqueued, for a struct_size
+ * smaller than the struct, a nonzero `reserved` or `reserved2`, N outside 0..2^25, S outside 1..64, C outside 1..256, H outside
+ * 1..8, num_octaves outside 1..16 (0 included: without an encoding GgrEpipolarAttnPass is the pass to call), a misaligned buffer,
+ * a ray tile (S rows of 4*(((4*ceil(C/4) + 4*ceil(E/4)) / 4) | 1) floats: 74 752 bytes at the most) that the device does not
+ * grant one workgroup as LDS, or (unless N == 0) a NULL required pointer: forward qk, qe, features, depth, out_ctx_f, out_ctx_e,
+ * out_attn; backward qk, qe, features, depth, attn, dL_dctx_f, dL_dctx_e, dL_dqk, dL_dqe, dL_dfeatures.  Element offsets are
+ * 64-bit: N*S*C may exceed 2^31. */
+typedef struct GgrEpipolarAttnEncPass {
+    int32_t struct_size;            /* sizeof(GgrEpipolarAttnEncPass) */
+    int32_t reserved;               /* 0 */
+    int32_t N;                      /* rays: 0..2^25 */
+    int32_t S;                      /* samples per ray: 1..64 */
+    int32_t C;                      /* channels of features: 1..256 */
+    int32_t H;                      /* heads: 1..8 */
+    int32_t num_octaves;            /* O of the positional encoding: 1..16; E = 2*O */
+    int32_t reserved2;              /* 0 */
+    const float* qk;                /* [N,H,C]: scale * Wk_h^T q_h */
+    const float* qe;                /* [N,H,E]: qk W */
+    const float* features;          /* [N,S,C] */
+    const float* depth;             /* [N,S] */
+    float* out_ctx_f;               /* forward: [N,H,C] */
+    float* out_ctx_e;               /* forward: [N,H,E] */
+    float* out_attn;                /* forward: [N,H,S] */
+    const float* attn;              /* backward: [N,H,S], the forward's out_attn */
+    const float* dL_dctx_f;         /* backward: [N,H,C] */
+    const float* dL_dctx_e;         /* backward: [N,H,E] */
+    float* dL_dqk;                  /* backward: [N,H,C], written whole */
+    float* dL_dqe;                  /* backward: [N,H,E], written whole */
+    float* dL_dfeatures;            /* backward: [N,S,C], written whole */
+    float* dL_ddepth;               /* backward: [N,S], written whole, or NULL */
+} GgrEpipolarAttnEncPass;
+
+int ggr_epipolar_attention_encoded_forward(const GgrEpipolarAttnEncPass* pass, void* stream);
+int ggr_epipolar_attention_encoded_backward(const GgrEpipolarAttnEncPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
