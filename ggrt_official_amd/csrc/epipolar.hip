@@ -294,6 +294,12 @@ epipolar_fwd_kernel(const EpipolarArgs a, const int total) {
     }
 }
 
+// the accumulator's zeroes, as a kernel: a node like the others when the launches are captured into a graph
+__global__ void __launch_bounds__(256)
+epipolar_zero_kernel(float* __restrict__ p, const size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0.f;
+}
+
 __global__ void __launch_bounds__(WAVE * WAVES)
 epipolar_bwd_kernel(const EpipolarArgs a, const int total) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -339,7 +345,8 @@ void launch_epipolar_forward(const EpipolarArgs& a, hipStream_t s) {
 void launch_epipolar_backward(const EpipolarArgs& a, hipStream_t s) {
     const int total = pair_rays(a);
     if (total <= 0) return;
-    hipMemsetAsync(a.scratch, 0, (size_t)a.b * a.v * a.h * a.w * a.c * sizeof(float), s);
+    const size_t cells = (size_t)a.b * a.v * a.h * a.w * a.c;
+    hipLaunchKernelGGL(epipolar_zero_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, s, a.scratch, cells);
     const int groups = std::min((total + WAVES - 1) / WAVES, kEpipolarMaxGroups);
     hipLaunchKernelGGL(epipolar_bwd_kernel, dim3((unsigned)groups), dim3(WAVE * WAVES), 0, s, a, total);
     hipLaunchKernelGGL(epipolar_from_channel_last_kernel, layout_grid(a), dim3(TT, 8), 0, s, a);

@@ -24,8 +24,8 @@ def other_views(v, device="cpu"):
 def _in_bounds(x, y, probe):
     if probe is not None:
         for q in (x, y):
-            probe.append((q, -1e-6))
-            probe.append((q, 1 + 1e-6))
+            probe.append((q, -1e-6, "point"))
+            probe.append((q, 1 + 1e-6, "point"))
     return (x >= -1e-6) & (y >= -1e-6) & (x <= 1 + 1e-6) & (y <= 1 + 1e-6)
 
 
@@ -37,7 +37,7 @@ def _point_projection(K, O, D, t, probe):
     x = K[..., 0, 0] * p[..., 0] + K[..., 0, 1] * p[..., 1] + K[..., 0, 2] * p[..., 2]
     y = K[..., 1, 0] * p[..., 0] + K[..., 1, 1] * p[..., 1] + K[..., 1, 2] * p[..., 2]
     if probe is not None:
-        probe.append((P[..., 2], -1e-6))
+        probe.append((P[..., 2], -1e-6, "point"))
     valid = _in_bounds(x, y, probe) & (P[..., 2] > -1e-6) & (t > -1e-6)
     return t.expand(valid.shape), x, y, valid
 
@@ -53,7 +53,7 @@ def _frame_intersection(K, O, D, dim, value, probe):
     same = torch.ones_like(other) * value
     z = oz + t * dz
     if probe is not None:
-        probe.extend([(other, -1e-6), (other, 1 + 1e-6), (z, -1e-6), (t, -1e-6)])
+        probe.extend([(other, -1e-6, "frame"), (other, 1 + 1e-6, "frame"), (z, -1e-6, "frame"), (t, -1e-6, "frame")])
     ok = (other >= -1e-6) & (other <= 1 + 1e-6) & (z > -1e-6) & (t > -1e-6)      # (the fixed coordinate is in bounds exactly)
     x, y = (same, other) if dim == 0 else (other, same)
     return t, x, y, ok
@@ -94,7 +94,7 @@ def _intersect(ox, dx, oy, dy, probe):
     """intersect_rays: the least-squares point of two rays, 1e10 where they are parallel"""
     dot = (dx * dy).sum(-1)
     if probe is not None:
-        probe.append((dot, 1 - 1e-5))
+        probe.append((dot, 1 - 1e-5, "dot"))
     eye = torch.eye(3, dtype=ox.dtype, device=ox.device)
     nx = dx[..., :, None] * dx[..., None, :] - eye
     ny = dy[..., :, None] * dy[..., None, :] - eye
@@ -159,7 +159,8 @@ def epipolar_reference(images, extrinsics, intrinsics, near, far, num_samples, r
                xy_sample_near=xy_min + (pos - half) * (xy_max - xy_min), xy_sample_far=xy_min + (pos + half) * (xy_max - xy_min),
                origins=origins, directions=directions, depth=depth)
     if details:
-        out.update(raw_depth=clipped, min_valid=nok, max_valid=fok)
+        out.update(raw_depth=clipped, min_valid=nok, max_valid=fok, near_xy=torch.stack([nx, ny], -1), far_xy=torch.stack([fx, fy], -1),
+                   near_z=(O + nr * D)[..., 2], far_z=(O + fr * D)[..., 2], dot=(dx * dy).sum(-1))
     return out
 
 
@@ -170,13 +171,27 @@ CASE_ARGS = ("images", "extrinsics", "intrinsics", "near", "far", "num_samples",
 def margin_violations(case):
     """The number of places where `case` breaks the margin rule: a validity quantity of any ray (an xy component of one of the
     six projections against 0 − 1e-6 and 1 + 1e-6, a camera-space z or a t against −1e-6) within 1e-4 of its threshold, a
-    direction dot product within 1e-4 of 1 − 1e-5, or a ray whose `valid` differs between the float32 and the float64 run."""
+    direction dot product within 1e-4 of 1 − 1e-5, or a ray whose `valid` differs between the float32 and the float64 run.
+
+    A case may carry `shared_centre`, bool [v, v-1]: the (view, other view) pairs whose two cameras stand at the same point, which
+    only the "rotation" family sets.  On those pairs, and on no others, two entries are left out: the frame-intersection
+    quantities (the casting origin is the sampled camera's centre, so t = 0/x and z = 0 exactly and `other` = 0/0 = NaN in
+    every precision: such a hit is refused whatever its t) and the dot product of their VALID rays (it is 1 up to rounding, on
+    the parallel side of the threshold by 1e-5; the test that uses the family asserts its own bound on it).  The point
+    projections, the dot products of invalid rays and the float32 / float64 comparison of `valid` stay."""
     args = {k: case[k] for k in CASE_ARGS}
+    shared = case.get("shared_centre")
     probe = []
     with torch.no_grad():
         ref = epipolar_reference(**args, probe=probe)
         low = epipolar_reference(**{k: (a.float() if torch.is_tensor(a) else a) for k, a in args.items()})
-    count = sum(int(((q - thr).abs() < MARGIN).sum()) for q, thr in probe)
+    count = 0
+    for q, thr, kind in probe:
+        close = (q - thr).abs() < MARGIN
+        if shared is not None and kind != "point":
+            skip = shared[None, :, :, None].expand(ref["valid"].shape)
+            close = close & ~((skip & ref["valid"])[..., None] if kind == "dot" else skip)
+        count += int(close.sum())
     return count + int((ref["valid"] != low["valid"]).sum())
 
 
@@ -193,8 +208,13 @@ def _look_at_z(yaw, pitch, position):
 # family: (yaw amplitude, baseline, near, far).  "default" is the family the sampler was first tried with; "inside" keeps most
 # segments wholly inside the other frame (near / far branches), "clipped" cuts most of them at the frame (frame-intersection
 # branches), "away" turns the views' backs to each other (nothing valid), "nearfar" gives every view its own near = far / 2.
+# "rotation": views 0 and 1 stand at the origin EXACTLY and differ by a yaw and a pitch of a few hundredths of a radian, so every
+# sample's ray of one is parallel to the casting ray of the other (intersect_rays' parallel branch); view 1's focal lengths are
+# about 0.6 against view 0's 0.9 … 1.1, so view 0's whole frame projects inside view 1 (segments from the near and far
+# projections; the frame intersections are 0/0 at a shared centre and are never consulted there).  Views 2 … are displaced as in
+# "default": parallel and non-parallel pairs in one call.
 FAMILIES = {"default": (0.15, 0.4, 1.0, 20.0), "inside": (0.066, 0.4, 2.0, 4.0), "clipped": (0.45, 1.2, 0.2, 100.0),
-            "away": (0.0, 0.4, 1.0, 20.0), "nearfar": (0.12, 0.4, None, None)}
+            "away": (0.0, 0.4, 1.0, 20.0), "nearfar": (0.12, 0.4, None, None), "rotation": (0.15, 0.4, 1.0, 20.0)}
 
 
 def _draw(b, v, h, w, c, s, seed, family, window):
@@ -213,12 +233,17 @@ def _draw(b, v, h, w, c, s, seed, family, window):
                     angle = 2 * math.pi * j / v + 0.05 * float(jitter[0])
                 pos = (0.3 * math.sin(angle), 0.0, 0.3 * math.cos(angle))     # each camera looks outwards from a small circle
                 ext[i, j] = _look_at_z(angle, 0.02 * float(jitter[1]), pos)
+            elif family == "rotation" and j < 2:
+                turn = (0.03 + 0.01 * float(jitter[0])) * (1 if j == 0 else -1)
+                ext[i, j] = _look_at_z(turn, 0.03 * float(jitter[1]), (0.0, 0.0, 0.0))
             else:
                 pos = (side * baseline + 0.05 * baseline * float(jitter[2]), 0.1 * baseline * float(jitter[3]), 0.05 * baseline * float(jitter[4]))
                 ext[i, j] = _look_at_z(-side * yaw + 0.03 * float(jitter[0]), 0.05 * float(jitter[1]), pos)
             k = rnd(4)
             K[i, j] = torch.tensor([[0.9 + 0.1 * float(k[0]), 0, 0.5 + 0.02 * float(k[1])], [0, 1.1 + 0.1 * float(k[2]), 0.5 + 0.02 * float(k[3])],
                                     [0, 0, 1]], dtype=torch.float64)
+            if family == "rotation" and j == 1:
+                K[i, j, 0, 0], K[i, j, 1, 1] = 0.6 + 0.02 * float(k[0]), 0.6 + 0.02 * float(k[2])
     if family == "nearfar":
         far_t = 8.0 + 4.0 * torch.arange(b * v, dtype=torch.float64).reshape(b, v) + rnd(b, v)
         near_t = far_t / 2
@@ -226,7 +251,11 @@ def _draw(b, v, h, w, c, s, seed, family, window):
         near_t = near * (1 + 0.05 * rnd(b, v))
         far_t = far * (1 + 0.05 * rnd(b, v))
     images = torch.randn(b, v, c, h, w, generator=gen, dtype=torch.float64)
-    return dict(images=images, extrinsics=ext, intrinsics=K, near=near_t, far=far_t, num_samples=s, ray_window=window)
+    case = dict(images=images, extrinsics=ext, intrinsics=K, near=near_t, far=far_t, num_samples=s, ray_window=window)
+    if family == "rotation":
+        idx = other_views(v)
+        case["shared_centre"] = (torch.arange(v)[:, None] < 2) & (idx < 2)
+    return case
 
 
 def make_case(b, v, h, w, c, s, seed, family="default", window=None, tries=4000):
