@@ -266,6 +266,19 @@ def epipolar_attn_enc_pass(**fields) -> GgrEpipolarAttnEncPass:
     return GgrEpipolarAttnEncPass(struct_size=C.sizeof(GgrEpipolarAttnEncPass), **fields)
 
 
+class GgrImageLossPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int32), ("channels", C.c_int32),
+                ("height", C.c_int32), ("width", C.c_int32), ("window_size", C.c_int32), ("size_average", C.c_int32),
+                ("pred", C.c_void_p), ("target", C.c_void_p), ("mask", C.c_void_p), ("out_mse", C.c_void_p), ("out_ssim", C.c_void_p),
+                ("mse_scale", C.c_void_p), ("partials", C.c_void_p), ("partials_bytes", C.c_int64), ("dL_dmse", C.c_void_p),
+                ("dL_dssim", C.c_void_p), ("dL_dpred", C.c_void_p), ("dL_dtarget", C.c_void_p)]
+
+
+def image_loss_pass(**fields) -> GgrImageLossPass:
+    """The argument of ggr_image_loss_forward / ggr_image_loss_backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrImageLossPass(struct_size=C.sizeof(GgrImageLossPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -358,6 +371,10 @@ SYMBOLS = [
     ("ggr_epipolar_attention_backward", C.c_int, [C.POINTER(GgrEpipolarAttnPass), C.c_void_p]),
     ("ggr_epipolar_attention_encoded_forward", C.c_int, [C.POINTER(GgrEpipolarAttnEncPass), C.c_void_p]),
     ("ggr_epipolar_attention_encoded_backward", C.c_int, [C.POINTER(GgrEpipolarAttnEncPass), C.c_void_p]),
+    ("ggr_image_loss_partials_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("ggr_image_loss_window", C.c_int, [C.c_int32, C.POINTER(C.c_float)]),
+    ("ggr_image_loss_forward", C.c_int, [C.POINTER(GgrImageLossPass), C.c_void_p]),
+    ("ggr_image_loss_backward", C.c_int, [C.POINTER(GgrImageLossPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

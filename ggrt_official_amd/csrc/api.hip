@@ -19,6 +19,7 @@
 #include "epipolar.h"
 #include "epipolar_attn.h"
 #include "epipolar_attn_enc.h"
+#include "image_loss.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1705,6 +1706,105 @@ int ggr_epipolar_attention_encoded_backward(const GgrEpipolarAttnEncPass* ap, vo
     if (rc) return rc;
     if (a.N == 0) return GGR_OK;
     return epipolar_attn_enc_launched(ggr::launch_epipolar_attn_enc_backward(a, (hipStream_t)stream), a, "epipolar_attention_encoded_backward");
+}
+
+// ---- the image loss (image_loss.hip): masked MSE and SSIM of two images, and the gradient with respect to either --------------
+namespace {
+bool image_loss_sizes_ok(int B, int C, int H, int W) {
+    return B >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= ggr::kImageLossMaxSide && W <= ggr::kImageLossMaxSide &&
+           (int64_t)B * C <= ggr::kImageLossMaxTiles && ggr::image_loss_tiles(1, 1, H, W) <= ggr::kImageLossMaxTiles / ((int64_t)B * C);
+}
+
+int image_loss_pass_check(const GgrImageLossPass* lp, bool backward, ggr::ImageLossArgs* a) {
+    if (!lp) return fail(GGR_E_INVALID, "null GgrImageLossPass");
+    if (lp->struct_size < (int32_t)sizeof(GgrImageLossPass))
+        return fail(GGR_E_INVALID, "GgrImageLossPass.struct_size %d is smaller than the %d bytes of its fields", (int)lp->struct_size,
+                    (int)sizeof(GgrImageLossPass));
+    if (lp->reserved != 0) return fail(GGR_E_INVALID, "GgrImageLossPass.reserved must be 0, not %d", (int)lp->reserved);
+    const int B = lp->batch, C = lp->channels, H = lp->height, W = lp->width, ws = lp->window_size;
+    if (B < 1) return fail(GGR_E_INVALID, "GgrImageLossPass.batch %d is below 1", B);
+    if (C < 1) return fail(GGR_E_INVALID, "GgrImageLossPass.channels %d is below 1", C);
+    if (H < 1 || H > ggr::kImageLossMaxSide) return fail(GGR_E_INVALID, "GgrImageLossPass.height %d is outside 1..%d", H, ggr::kImageLossMaxSide);
+    if (W < 1 || W > ggr::kImageLossMaxSide) return fail(GGR_E_INVALID, "GgrImageLossPass.width %d is outside 1..%d", W, ggr::kImageLossMaxSide);
+    if (!image_loss_sizes_ok(B, C, H, W))
+        return fail(GGR_E_INVALID, "GgrImageLossPass: batch %d x channels %d x height %d x width %d is more than %lld tiles", B, C, H, W,
+                    (long long)ggr::kImageLossMaxTiles);
+    if (ws < 1 || ws > ggr::kImageLossMaxWindow || ws % 2 == 0)
+        return fail(GGR_E_INVALID, "GgrImageLossPass.window_size %d is not an odd number in 1..%d", ws, ggr::kImageLossMaxWindow);
+    if (lp->size_average != 0 && lp->size_average != 1)
+        return fail(GGR_E_INVALID, "GgrImageLossPass.size_average must be 0 or 1, not %d", (int)lp->size_average);
+    if (!backward) {
+        const void* in[] = {lp->pred, lp->target, lp->out_mse, lp->out_ssim, lp->mse_scale, lp->partials};
+        const char* name[] = {"pred", "target", "out_mse", "out_ssim", "mse_scale", "partials"};
+        for (int i = 0; i < 6; ++i)
+            if (!in[i]) return fail(GGR_E_INVALID, "GgrImageLossPass.%s is NULL", name[i]);
+        const int64_t need = ggr::image_loss_tiles(B, C, H, W) * ggr::kImageLossPartials * (int64_t)sizeof(double);
+        if (lp->partials_bytes < need)
+            return fail(GGR_E_INVALID, "GgrImageLossPass.partials_bytes %lld is smaller than the %lld bytes the pass needs", (long long)lp->partials_bytes,
+                        (long long)need);
+        if (((uintptr_t)lp->partials & 7u) != 0) return fail(GGR_E_INVALID, "GgrImageLossPass.partials is misaligned (it needs 8-byte alignment)");
+    } else {
+        const void* in[] = {lp->pred, lp->target, lp->mse_scale};
+        const char* name[] = {"pred", "target", "mse_scale"};
+        for (int i = 0; i < 3; ++i)
+            if (!in[i]) return fail(GGR_E_INVALID, "GgrImageLossPass.%s is NULL", name[i]);
+        if (!lp->dL_dmse && !lp->dL_dssim) return fail(GGR_E_INVALID, "GgrImageLossPass.dL_dmse and dL_dssim are both NULL");
+        if (!lp->dL_dpred && !lp->dL_dtarget) return fail(GGR_E_INVALID, "GgrImageLossPass.dL_dpred and dL_dtarget are both NULL");
+    }
+    const void* all[] = {lp->pred, lp->target, lp->mask, lp->out_mse, lp->out_ssim, lp->mse_scale, lp->dL_dmse, lp->dL_dssim, lp->dL_dpred, lp->dL_dtarget};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrImageLossPass: a buffer is misaligned (every float array needs 4-byte alignment)");
+    a->B = B; a->C = C; a->H = H; a->W = W; a->window = ws; a->size_average = lp->size_average;
+    a->pred = lp->pred; a->target = lp->target; a->mask = lp->mask; a->mse = lp->out_mse; a->ssim = lp->out_ssim; a->mse_scale = lp->mse_scale;
+    a->partials = (double*)lp->partials; a->g_mse = lp->dL_dmse; a->g_ssim = lp->dL_dssim; a->g_image = nullptr;
+    ggr::image_loss_window(ws, a->w);
+    return GGR_OK;
+}
+}  // namespace
+
+int64_t ggr_image_loss_partials_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+    if (!image_loss_sizes_ok(batch, channels, height, width)) return -1;
+    return ggr::image_loss_tiles(batch, channels, height, width) * ggr::kImageLossPartials * (int64_t)sizeof(double);
+}
+
+int ggr_image_loss_window(int32_t window_size, float* out) {
+    g_err[0] = 0;
+    if (window_size < 1 || window_size > ggr::kImageLossMaxWindow || window_size % 2 == 0)
+        return fail(GGR_E_INVALID, "ggr_image_loss_window: window_size %d is not an odd number in 1..%d", (int)window_size, ggr::kImageLossMaxWindow);
+    if (!out) return fail(GGR_E_INVALID, "ggr_image_loss_window: out is NULL");
+    float w[ggr::kImageLossMaxWindow];
+    ggr::image_loss_window(window_size, w);
+    memcpy(out, w, sizeof(float) * (size_t)window_size);
+    return GGR_OK;
+}
+
+int ggr_image_loss_forward(const GgrImageLossPass* lp, void* stream) {
+    g_err[0] = 0;
+    ggr::ImageLossArgs a;
+    const int rc = image_loss_pass_check(lp, false, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_image_loss_forward(a, s);
+    KCHECK(false, s, "image_loss_forward");
+    return GGR_OK;
+}
+
+int ggr_image_loss_backward(const GgrImageLossPass* lp, void* stream) {
+    g_err[0] = 0;
+    ggr::ImageLossArgs a;
+    const int rc = image_loss_pass_check(lp, true, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (lp->dL_dpred) {
+        a.g_image = lp->dL_dpred;
+        ggr::launch_image_loss_backward(a, s);
+    }
+    if (lp->dL_dtarget) {      // SSIM is symmetric and the MSE term changes its sign with the difference: the same kernel, roles exchanged
+        a.pred = lp->target; a.target = lp->pred; a.g_image = lp->dL_dtarget;
+        ggr::launch_image_loss_backward(a, s);
+    }
+    KCHECK(false, s, "image_loss_backward");
+    return GGR_OK;
 }
 
 // ---- the distortion pass (blend_dist.hip): the depth-distortion plane over a forward's lists, and its backward -----------------

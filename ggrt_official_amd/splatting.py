@@ -30,7 +30,7 @@ from __future__ import annotations
 import os
 from dataclasses import dataclass
 from math import isqrt
-from typing import Literal, Optional
+from typing import Literal, NamedTuple, Optional
 
 import ctypes as C
 
@@ -740,6 +740,131 @@ def fused_epipolar_encoded_attention(x: Tensor, features: Tensor, depth: Tensor,
         out = torch.nn.functional.linear(out, f32(w_out), None if b_out is None else f32(b_out))
     out = out.reshape(x.shape)
     return (out, attn) if return_weights else out
+
+
+class ImageLoss(NamedTuple):
+    """What ``fused_image_loss`` returns: both fields are differentiable; shape [] with ``size_average``, otherwise [B]."""
+    mse: Tensor
+    ssim: Tensor
+
+    @property
+    def psnr(self) -> Tensor:
+        """The reference's ``mse2psnr``: −10·log10(mse + 1e-6), a torch expression on ``mse``."""
+        return -10.0 * torch.log10(self.mse + 1e-6)
+
+
+# tests only: True fills every buffer the image-loss launches must write whole with NaN before the launch
+_IMAGE_LOSS_POISON = False
+
+
+def _image_loss_buffer(shape, dev, dtype=torch.float32):
+    if _IMAGE_LOSS_POISON:
+        return torch.full(shape, float("nan"), dtype=dtype, device=dev)
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
+class _FusedImageLoss(torch.autograd.Function):
+    """ggr_image_loss_forward / ggr_image_loss_backward (csrc/image_loss.hip) behind autograd: pred, target [B,C,H,W] and mask
+    [B,H,W] or None, float32 and contiguous on arrival → mse, ssim.  Only the inputs and the mse denominator are saved."""
+
+    @staticmethod
+    def _call(name, dev, dims, **pointers):
+        b, c, h, w, window, size_average = dims
+        lp = _lib.image_loss_pass(reserved=0, batch=b, channels=c, height=h, width=w, window_size=window, size_average=int(size_average),
+                                  **pointers)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.load(), name)(C.byref(lp), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, window_size, size_average):
+        dev = pred.device
+        b, c, h, w = pred.shape
+        dims = (b, c, h, w, window_size, size_average)
+        shape = () if size_average else (b,)
+        mse, ssim, scale = (_image_loss_buffer(shape, dev) for _ in range(3))
+        nbytes = int(_lib.load().ggr_image_loss_partials_bytes(b, c, h, w))
+        if nbytes < 0:
+            raise ValueError(f"fused_image_loss: pred {tuple(pred.shape)} is larger than the pass takes")
+        partials = _image_loss_buffer((nbytes // 8,), dev, torch.float64)
+        _FusedImageLoss._call("ggr_image_loss_forward", dev, dims, pred=pred.data_ptr(), target=target.data_ptr(),
+                              mask=None if mask is None else mask.data_ptr(), out_mse=mse.data_ptr(), out_ssim=ssim.data_ptr(),
+                              mse_scale=scale.data_ptr(), partials=partials.data_ptr(), partials_bytes=nbytes)
+        ctx.dims = dims
+        ctx.has_mask = mask is not None
+        ctx.set_materialize_grads(False)     # (a field nobody used arrives as None and goes to the launch as NULL)
+        ctx.save_for_backward(pred, target, scale, *(() if mask is None else (mask,)))
+        return mse, ssim
+
+    @staticmethod
+    def backward(ctx, g_mse, g_ssim):
+        if g_mse is None and g_ssim is None:
+            return None, None, None, None, None
+        pred, target, scale = ctx.saved_tensors[:3]
+        mask = ctx.saved_tensors[3] if ctx.has_mask else None
+        dev = pred.device
+        ptr = lambda t: None if t is None else t.data_ptr()
+        f = lambda t: None if t is None else t.to(dtype=torch.float32).contiguous()
+        g_mse, g_ssim = f(g_mse), f(g_ssim)
+        d_pred = _image_loss_buffer(tuple(pred.shape), dev) if ctx.needs_input_grad[0] else None
+        d_target = _image_loss_buffer(tuple(pred.shape), dev) if ctx.needs_input_grad[1] else None
+        if d_pred is not None or d_target is not None:
+            _FusedImageLoss._call("ggr_image_loss_backward", dev, ctx.dims, pred=pred.data_ptr(), target=target.data_ptr(), mask=ptr(mask),
+                                  mse_scale=scale.data_ptr(), dL_dmse=ptr(g_mse), dL_dssim=ptr(g_ssim), dL_dpred=ptr(d_pred),
+                                  dL_dtarget=ptr(d_target))
+        return d_pred, d_target, None, None, None
+
+
+def fused_image_loss(pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, *, window_size: int = 11,
+                     size_average: bool = True) -> ImageLoss:
+    """GGRt's training loss ``img2mse(x, y, mask)`` (``utils_loc.py``) and its evaluation metric ``ssim(img1, img2, window_size,
+    size_average)`` (``ggrt/loss/ssim_torch.py``) of a rendered image against its target as one HIP launch plus a small finishing
+    one, and one launch per image for the backward (the arithmetic: ``GgrImageLossPass`` in
+    include/ggr_raster.h).  ``pred`` / ``target`` [B,C,H,W] float32 on the GPU — or [C,H,W], the rasterizer's own output, taken as
+    B = 1; ``mask`` [B,H,W] (or [H,W]) float weights of the MSE, which is then Σ d²·mask / (Σ mask·C + 1e-6); the mask does not
+    enter SSIM and gets no gradient.  ``size_average=False`` gives one value per image, each MSE with its own mask slice.  Returns
+    ``ImageLoss(mse, ssim)`` (and ``.psnr``): both differentiable with respect to ``pred`` and ``target``; a field that the loss does
+    not use costs nothing in the backward (with ``mse`` alone the backward is one element-wise pass).  Non-contiguous inputs are
+    made contiguous; two runs give the same bits."""
+    for name, t in (("pred", pred), ("target", target), ("mask", mask)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise ValueError(f"fused_image_loss: {name} is not a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"fused_image_loss: {name} is on {t.device}; the pass runs on the GPU only (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"fused_image_loss: {name} is {t.dtype}, not torch.float32")
+    if pred.dim() not in (3, 4):
+        raise ValueError(f"fused_image_loss: pred {tuple(pred.shape)} is neither [B, C, H, W] nor [C, H, W]")
+    if tuple(target.shape) != tuple(pred.shape):
+        raise ValueError(f"fused_image_loss: target {tuple(target.shape)} does not have the shape of pred {tuple(pred.shape)}")
+    if target.device != pred.device or (mask is not None and mask.device != pred.device):
+        raise RuntimeError("fused_image_loss: pred, target and mask are not on one device")
+    window_size = int(window_size)
+    if window_size < 1 or window_size > 11 or window_size % 2 == 0:
+        raise ValueError(f"fused_image_loss: window_size {window_size} is not an odd number in 1..11")
+    if pred.numel() == 0:
+        raise ValueError(f"fused_image_loss: pred {tuple(pred.shape)} has no elements")
+    batched = pred.dim() == 4
+    if mask is not None:
+        if mask.requires_grad:
+            raise RuntimeError("fused_image_loss: mask requires grad, but there is no gradient with respect to the mask (detach it)")
+        want = (pred.shape[0],) + tuple(pred.shape[2:]) if batched else tuple(pred.shape[1:])
+        if tuple(mask.shape) != want:
+            raise ValueError(f"fused_image_loss: mask {tuple(mask.shape)} is not {list(want)} for pred {tuple(pred.shape)}")
+        mask = (mask if batched else mask[None]).contiguous()
+    if not batched:
+        pred, target = pred[None], target[None]
+    mse, ssim = _FusedImageLoss.apply(pred.contiguous(), target.contiguous(), mask, window_size, bool(size_average))
+    return ImageLoss(mse=mse, ssim=ssim)
+
+
+def fused_ssim(img1: Tensor, img2: Tensor, window_size: int = 11, size_average: bool = True) -> Tensor:
+    """The reference's ``ssim(img1, img2, window_size, size_average)`` (``ggrt/loss/ssim_torch.py``) with the same signature and
+    meaning, through ``fused_image_loss``: differentiable with respect to both images."""
+    return fused_image_loss(img1, img2, None, window_size=window_size, size_average=size_average).ssim
 
 
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,

@@ -1146,6 +1146,58 @@ typedef struct GgrEpipolarAttnEncPass {
 int ggr_epipolar_attention_encoded_forward(const GgrEpipolarAttnEncPass* pass, void* stream);
 int ggr_epipolar_attention_encoded_backward(const GgrEpipolarAttnEncPass* pass, void* stream);
 
+/* The image loss behind the blend: GGRt's img2mse (utils_loc.py:49-60) and ssim (ggrt/loss/ssim_torch.py) of pred against target,
+ * both [B,C,H,W] float32 dense, with an optional float weight mask [B,H,W]; nout = size_average ? 1 : B results each.
+ *     mse[o]  = sum (pred - target)^2 * mask / (sum(mask) * C + 1e-6)        without a mask: the plain mean
+ *     ssim[o] = mean of ((2 mu1 mu2 + C1)(2 sig12 + C2)) / ((mu1^2 + mu2^2 + C1)(sig1 + sig2 + C2)),   C1 = 0.01^2, C2 = 0.03^2
+ * where mu1 = w * pred, mu2 = w * target, sig1 = w * pred^2 - mu1^2, sig2 = w * target^2 - mu2^2, sig12 = w * (pred target) - mu1 mu2
+ * and `w *` is the per-channel convolution with the window_size x window_size Gaussian (sigma 1.5) the reference builds, with
+ * zero padding of window_size / 2; it is applied separably (rows, then columns) with the reference's float32 1-D window
+ * (ggr_image_loss_window).  The mask does not enter ssim.  With size_average the sums run over the whole batch, otherwise over
+ * image o alone (its own mask slice).  An all-zero mask gives mse = 0.
+ * ggr_image_loss_forward: pred, target, mask (or NULL) -> out_mse, out_ssim, mse_scale [nout] (the reciprocal of the mse
+ *     denominator: state for the backward), using `partials` (ggr_image_loss_partials_bytes, 8-byte aligned) as scratch.  One
+ *     launch over 16 x 32 tiles of the planes and one small finishing launch.
+ * ggr_image_loss_backward: pred, target, mask, mse_scale, dL_dmse and dL_dssim [nout] (either may be NULL: that result contributes
+ *     nothing) -> dL_dpred and / or dL_dtarget [B,C,H,W] (each written whole; NULL: not computed; one launch each).  Nothing else of
+ *     the forward is needed: the window sums are recomputed.  There is no gradient with respect to the mask.
+ * No atomics and a fixed order of summation: two calls on the same inputs give the same bits.  Non-finite pixels give non-finite
+ * results, as in the reference.  Both calls allocate nothing, set no memory, read nothing back, are ordered on `stream`, do not
+ * synchronise and are hipGraph-capturable.  GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct,
+ * a nonzero `reserved`, batch / channels / height / width below 1 (height, width above 2^20, more than 2^30 tiles), window_size
+ * even or outside 1..11, size_average other than 0 or 1, a misaligned buffer, partials_bytes too small, or a NULL required
+ * pointer: forward pred, target, out_mse, out_ssim, mse_scale, partials; backward pred, target, mse_scale, one of dL_dmse /
+ * dL_dssim and one of dL_dpred / dL_dtarget.  Element offsets are 64-bit. */
+typedef struct GgrImageLossPass {
+    int32_t struct_size;            /* sizeof(GgrImageLossPass) */
+    int32_t reserved;               /* 0 */
+    int32_t batch;                  /* B >= 1 */
+    int32_t channels;               /* C >= 1 */
+    int32_t height;                 /* H: 1..2^20 */
+    int32_t width;                  /* W: 1..2^20 */
+    int32_t window_size;            /* 1, 3, 5, 7, 9 or 11 */
+    int32_t size_average;           /* 1: one result over the batch; 0: one per image */
+    const float* pred;              /* [B,C,H,W] */
+    const float* target;            /* [B,C,H,W] */
+    const float* mask;              /* [B,H,W] float weights, or NULL */
+    float* out_mse;                 /* forward: [nout] */
+    float* out_ssim;                /* forward: [nout] */
+    float* mse_scale;               /* [nout]: written by the forward, read by the backward */
+    void* partials;                 /* forward: scratch of partials_bytes */
+    int64_t partials_bytes;
+    const float* dL_dmse;           /* backward: [nout], or NULL */
+    const float* dL_dssim;          /* backward: [nout], or NULL */
+    float* dL_dpred;                /* backward: [B,C,H,W], written whole, or NULL */
+    float* dL_dtarget;              /* backward: [B,C,H,W], written whole, or NULL */
+} GgrImageLossPass;
+
+/* bytes of GgrImageLossPass.partials (24 per tile), or -1 for sizes that the pass refuses */
+int64_t ggr_image_loss_partials_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width);
+/* the normalised 1-D window (host memory, window_size floats): the reference's gaussian(window_size, 1.5), bit for bit.  No GPU work. */
+int ggr_image_loss_window(int32_t window_size, float* out);
+int ggr_image_loss_forward(const GgrImageLossPass* pass, void* stream);
+int ggr_image_loss_backward(const GgrImageLossPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
