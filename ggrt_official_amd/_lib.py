@@ -279,6 +279,22 @@ def image_loss_pass(**fields) -> GgrImageLossPass:
     return GgrImageLossPass(struct_size=C.sizeof(GgrImageLossPass), **fields)
 
 
+class GgrPhotometricLossPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("num_views", C.c_int32), ("num_iters", C.c_int32),
+                ("height", C.c_int32), ("width", C.c_int32), ("automask", C.c_int32), ("reserved2", C.c_int32),
+                ("ssim_loss_weight", C.c_float), ("smooth_loss_weight", C.c_float), ("C1", C.c_float), ("C2", C.c_float),
+                ("clip_loss", C.c_float), ("gamma", C.c_float), ("image", C.c_void_p), ("ref_imgs", C.c_void_p),
+                ("inv_depths", C.c_void_p), ("K", C.c_void_p), ("ref_Ks", C.c_void_p), ("poses", C.c_void_p), ("planes", C.c_void_p),
+                ("planes_bytes", C.c_int64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out_thresholds", C.c_void_p),
+                ("state", C.c_void_p), ("choice", C.c_void_p), ("out_loss", C.c_void_p), ("out_photometric", C.c_void_p),
+                ("out_smoothness", C.c_void_p), ("dL_dloss", C.c_void_p), ("dL_dinv_depths", C.c_void_p), ("dL_dposes", C.c_void_p)]
+
+
+def photometric_loss_pass(**fields) -> GgrPhotometricLossPass:
+    """The argument of ggr_photometric_loss_forward / _backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrPhotometricLossPass(struct_size=C.sizeof(GgrPhotometricLossPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -375,6 +391,10 @@ SYMBOLS = [
     ("ggr_image_loss_window", C.c_int, [C.c_int32, C.POINTER(C.c_float)]),
     ("ggr_image_loss_forward", C.c_int, [C.POINTER(GgrImageLossPass), C.c_void_p]),
     ("ggr_image_loss_backward", C.c_int, [C.POINTER(GgrImageLossPass), C.c_void_p]),
+    ("ggr_photometric_loss_planes_bytes", C.c_int64, [C.c_int32] * 5),
+    ("ggr_photometric_loss_workspace_bytes", C.c_int64, [C.c_int32] * 5),
+    ("ggr_photometric_loss_forward", C.c_int, [C.POINTER(GgrPhotometricLossPass), C.c_void_p]),
+    ("ggr_photometric_loss_backward", C.c_int, [C.POINTER(GgrPhotometricLossPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

@@ -20,6 +20,7 @@
 #include "epipolar_attn.h"
 #include "epipolar_attn_enc.h"
 #include "image_loss.h"
+#include "photometric_loss.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1804,6 +1805,106 @@ int ggr_image_loss_backward(const GgrImageLossPass* lp, void* stream) {
         ggr::launch_image_loss_backward(a, s);
     }
     KCHECK(false, s, "image_loss_backward");
+    return GGR_OK;
+}
+
+// ---- the multi-view photometric loss (photometric_loss.hip) ----------------------------------------------------------------------
+namespace {
+bool photo_loss_sizes_ok(int V, int n, int H, int W, int automask) {
+    return V >= 1 && n >= 1 && n <= ggr::kPhotoMaxIters && H >= 2 && W >= 2 && H <= ggr::kPhotoMaxSide && W <= ggr::kPhotoMaxSide &&
+           (automask == 0 || automask == 1) && (int64_t)V * (automask ? 2 : 1) <= ggr::kPhotoMaxCandidates;
+}
+
+int photo_loss_pass_check(const GgrPhotometricLossPass* lp, bool backward, ggr::PhotoLossArgs* a) {
+    if (!lp) return fail(GGR_E_INVALID, "null GgrPhotometricLossPass");
+    if (lp->struct_size < (int32_t)sizeof(GgrPhotometricLossPass))
+        return fail(GGR_E_INVALID, "GgrPhotometricLossPass.struct_size %d is smaller than the %d bytes of its fields", (int)lp->struct_size,
+                    (int)sizeof(GgrPhotometricLossPass));
+    if (lp->reserved != 0 || lp->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrPhotometricLossPass.reserved must be 0, not %d / %d", (int)lp->reserved, (int)lp->reserved2);
+    const int V = lp->num_views, n = lp->num_iters, H = lp->height, W = lp->width;
+    if (V < 1) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.num_views %d is below 1", V);
+    if (n < 1 || n > ggr::kPhotoMaxIters) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.num_iters %d is outside 1..%d", n, ggr::kPhotoMaxIters);
+    if (H < 2 || H > ggr::kPhotoMaxSide) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.height %d is outside 2..%d", H, ggr::kPhotoMaxSide);
+    if (W < 2 || W > ggr::kPhotoMaxSide) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.width %d is outside 2..%d", W, ggr::kPhotoMaxSide);
+    if (lp->automask != 0 && lp->automask != 1) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.automask must be 0 or 1, not %d", (int)lp->automask);
+    const int C = V * (lp->automask ? 2 : 1);
+    if (!photo_loss_sizes_ok(V, n, H, W, lp->automask))
+        return fail(GGR_E_INVALID, "GgrPhotometricLossPass: %d views make %d candidates per pixel, more than the %d the pass takes", V, C,
+                    ggr::kPhotoMaxCandidates);
+    if (!(lp->ssim_loss_weight > 0.f && lp->ssim_loss_weight <= 1.f))
+        return fail(GGR_E_INVALID, "GgrPhotometricLossPass.ssim_loss_weight %g is not in (0, 1]", (double)lp->ssim_loss_weight);
+    const float nonneg[] = {lp->smooth_loss_weight, lp->C1, lp->C2, lp->clip_loss, lp->gamma};
+    const char* nname[] = {"smooth_loss_weight", "C1", "C2", "clip_loss", "gamma"};
+    for (int i = 0; i < 5; ++i)
+        if (!(nonneg[i] >= 0.f && nonneg[i] <= 3.0e38f)) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.%s %g is negative or not finite", nname[i], (double)nonneg[i]);
+    {
+        const void* in[] = {lp->image, lp->ref_imgs, lp->inv_depths, lp->K, lp->ref_Ks, lp->poses, lp->planes, lp->workspace, lp->out_thresholds, lp->state, lp->choice};
+        const char* name[] = {"image", "ref_imgs", "inv_depths", "K", "ref_Ks", "poses", "planes", "workspace", "out_thresholds", "state", "choice"};
+        for (int i = 0; i < 11; ++i)
+            if (!in[i]) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.%s is NULL", name[i]);
+    }
+    if (!backward) {
+        const void* in[] = {lp->out_loss, lp->out_photometric, lp->out_smoothness};
+        const char* name[] = {"out_loss", "out_photometric", "out_smoothness"};
+        for (int i = 0; i < 3; ++i)
+            if (!in[i]) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.%s is NULL", name[i]);
+    } else {
+        const void* in[] = {lp->dL_dloss, lp->dL_dinv_depths, lp->dL_dposes};
+        const char* name[] = {"dL_dloss", "dL_dinv_depths", "dL_dposes"};
+        for (int i = 0; i < 3; ++i)
+            if (!in[i]) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.%s is NULL", name[i]);
+    }
+    const int64_t need_planes = ggr::photo_loss_planes(V, n, lp->automask) * H * W * (int64_t)sizeof(float);
+    const int64_t need_ws = ggr::photo_loss_workspace_doubles(V, n, H, W, lp->automask) * (int64_t)sizeof(double);
+    if (lp->planes_bytes < need_planes)
+        return fail(GGR_E_INVALID, "GgrPhotometricLossPass.planes_bytes %lld is smaller than the %lld bytes the pass needs", (long long)lp->planes_bytes, (long long)need_planes);
+    if (lp->workspace_bytes < need_ws)
+        return fail(GGR_E_INVALID, "GgrPhotometricLossPass.workspace_bytes %lld is smaller than the %lld bytes the pass needs", (long long)lp->workspace_bytes, (long long)need_ws);
+    if (((uintptr_t)lp->workspace & 7u) != 0) return fail(GGR_E_INVALID, "GgrPhotometricLossPass.workspace is misaligned (it needs 8-byte alignment)");
+    const void* all[] = {lp->image, lp->ref_imgs, lp->inv_depths, lp->K, lp->ref_Ks, lp->poses, lp->planes, lp->out_thresholds, lp->state, lp->out_loss,
+                         lp->out_photometric, lp->out_smoothness, lp->dL_dloss, lp->dL_dinv_depths, lp->dL_dposes};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrPhotometricLossPass: a buffer is misaligned (every float array needs 4-byte alignment)");
+    a->V = V; a->n = n; a->H = H; a->W = W; a->automask = lp->automask; a->clip_on = lp->clip_loss > 0.f; a->C = C;
+    a->w_ssim = lp->ssim_loss_weight; a->w_smooth = lp->smooth_loss_weight; a->C1 = lp->C1; a->C2 = lp->C2; a->clip = lp->clip_loss; a->gamma = lp->gamma;
+    a->image = lp->image; a->ref_imgs = lp->ref_imgs; a->inv_depths = lp->inv_depths; a->K = lp->K; a->ref_Ks = lp->ref_Ks; a->poses = lp->poses;
+    a->planes = lp->planes; a->workspace = (double*)lp->workspace; a->thresholds = lp->out_thresholds; a->state = lp->state; a->choice = lp->choice;
+    a->loss = lp->out_loss; a->photo = lp->out_photometric; a->smooth = lp->out_smoothness;
+    a->g_loss = lp->dL_dloss; a->g_inv = lp->dL_dinv_depths; a->g_poses = lp->dL_dposes;
+    return GGR_OK;
+}
+}  // namespace
+
+int64_t ggr_photometric_loss_planes_bytes(int32_t num_views, int32_t num_iters, int32_t height, int32_t width, int32_t automask) {
+    if (!photo_loss_sizes_ok(num_views, num_iters, height, width, automask)) return -1;
+    return ggr::photo_loss_planes(num_views, num_iters, automask) * height * width * (int64_t)sizeof(float);
+}
+
+int64_t ggr_photometric_loss_workspace_bytes(int32_t num_views, int32_t num_iters, int32_t height, int32_t width, int32_t automask) {
+    if (!photo_loss_sizes_ok(num_views, num_iters, height, width, automask)) return -1;
+    return ggr::photo_loss_workspace_doubles(num_views, num_iters, height, width, automask) * (int64_t)sizeof(double);
+}
+
+int ggr_photometric_loss_forward(const GgrPhotometricLossPass* lp, void* stream) {
+    g_err[0] = 0;
+    ggr::PhotoLossArgs a;
+    const int rc = photo_loss_pass_check(lp, false, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_photo_loss_forward(a, s);
+    KCHECK(false, s, "photometric_loss_forward");
+    return GGR_OK;
+}
+
+int ggr_photometric_loss_backward(const GgrPhotometricLossPass* lp, void* stream) {
+    g_err[0] = 0;
+    ggr::PhotoLossArgs a;
+    const int rc = photo_loss_pass_check(lp, true, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_photo_loss_backward(a, s);
+    KCHECK(false, s, "photometric_loss_backward");
     return GGR_OK;
 }
 

@@ -867,6 +867,179 @@ def fused_ssim(img1: Tensor, img2: Tensor, window_size: int = 11, size_average: 
     return fused_image_loss(img1, img2, None, window_size=window_size, size_average=size_average).ssim
 
 
+class PhotometricLoss(NamedTuple):
+    """What ``fused_photometric_loss`` returns.  ``loss`` [1] is differentiable; ``photometric_loss`` and ``smoothness_loss`` [] are
+    the reference's two metrics, detached; ``thresholds`` [n, C] the clip values; ``choice`` [n, H, W] uint8 the candidate that won
+    each pixel's minimum (``choice % 2 == 1`` is Monodepth2's auto-mask), or None without ``return_choice``."""
+    loss: Tensor
+    photometric_loss: Tensor
+    smoothness_loss: Tensor
+    thresholds: Tensor
+    choice: Optional[Tensor]
+
+
+PHOTOMETRIC_MAX_CANDIDATES = 16     # kPhotoMaxCandidates of csrc/photometric_loss.h: V <= 8 with the auto-mask, V <= 16 without
+
+
+class _FusedPhotometricLoss(torch.autograd.Function):
+    """ggr_photometric_loss_forward / _backward (csrc/photometric_loss.hip) behind autograd: float32 contiguous tensors on arrival
+    (inv_depths [n,H,W], poses [V,n,6]) → loss, metrics, thresholds, choice.  The candidate planes, the thresholds, the choice
+    and 2n numbers of state are saved; every buffer comes from torch."""
+
+    @staticmethod
+    def _call(name, dev, dims, opts, **pointers):
+        v, n, h, w, automask = dims
+        lp = _lib.photometric_loss_pass(reserved=0, num_views=v, num_iters=n, height=h, width=w, automask=int(automask), reserved2=0,
+                                        **opts, **pointers)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.load(), name)(C.byref(lp), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+    @staticmethod
+    def forward(ctx, inv_depths, poses, image, ref_imgs, K, ref_Ks, automask, opts):
+        dev = image.device
+        n, h, w = inv_depths.shape
+        v = ref_imgs.shape[0]
+        dims = (v, n, h, w, automask)
+        c = v * (2 if automask else 1)
+        lib = _lib.load()
+        planes_bytes, ws_bytes = int(lib.ggr_photometric_loss_planes_bytes(v, n, h, w, int(automask))), int(lib.ggr_photometric_loss_workspace_bytes(v, n, h, w, int(automask)))
+        if planes_bytes < 0 or ws_bytes < 0:
+            raise ValueError(f"fused_photometric_loss: {v} views x {n} iterations at {h} x {w} is more than the pass takes")
+        planes = _image_loss_buffer((planes_bytes // 4,), dev)
+        workspace = _image_loss_buffer((ws_bytes // 8,), dev, torch.float64)
+        thresholds, state = _image_loss_buffer((n, c), dev), _image_loss_buffer((2 * n,), dev)
+        choice = torch.full((n, h, w), 255, dtype=torch.uint8, device=dev) if _IMAGE_LOSS_POISON else torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+        loss, photo, smooth = _image_loss_buffer((1,), dev), _image_loss_buffer((), dev), _image_loss_buffer((), dev)
+        fixed = dict(image=image.data_ptr(), ref_imgs=ref_imgs.data_ptr(), inv_depths=inv_depths.data_ptr(), K=K.data_ptr(), ref_Ks=ref_Ks.data_ptr(),
+                     poses=poses.data_ptr(), planes=planes.data_ptr(), planes_bytes=planes_bytes, out_thresholds=thresholds.data_ptr(),
+                     state=state.data_ptr(), choice=choice.data_ptr())
+        _FusedPhotometricLoss._call("ggr_photometric_loss_forward", dev, dims, opts, workspace=workspace.data_ptr(), workspace_bytes=ws_bytes,
+                                    out_loss=loss.data_ptr(), out_photometric=photo.data_ptr(), out_smoothness=smooth.data_ptr(), **fixed)
+        ctx.dims, ctx.opts, ctx.ws_bytes, ctx.planes_bytes = dims, opts, ws_bytes, planes_bytes
+        ctx.save_for_backward(inv_depths, poses, image, ref_imgs, K, ref_Ks, planes, thresholds, state, choice)
+        ctx.mark_non_differentiable(photo, smooth, thresholds, choice)
+        ctx.set_materialize_grads(False)
+        return loss, photo, smooth, thresholds, choice
+
+    @staticmethod
+    def backward(ctx, g_loss, *_):
+        if g_loss is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 8
+        inv_depths, poses, image, ref_imgs, K, ref_Ks, planes, thresholds, state, choice = ctx.saved_tensors
+        dev = image.device
+        g_loss = g_loss.to(dtype=torch.float32).contiguous()
+        workspace = _image_loss_buffer((ctx.ws_bytes // 8,), dev, torch.float64)
+        d_inv, d_poses = _image_loss_buffer(tuple(inv_depths.shape), dev), _image_loss_buffer(tuple(poses.shape), dev)
+        _FusedPhotometricLoss._call("ggr_photometric_loss_backward", dev, ctx.dims, ctx.opts, image=image.data_ptr(), ref_imgs=ref_imgs.data_ptr(),
+                                    inv_depths=inv_depths.data_ptr(), K=K.data_ptr(), ref_Ks=ref_Ks.data_ptr(), poses=poses.data_ptr(),
+                                    planes=planes.data_ptr(), planes_bytes=ctx.planes_bytes, out_thresholds=thresholds.data_ptr(),
+                                    state=state.data_ptr(), choice=choice.data_ptr(), workspace=workspace.data_ptr(), workspace_bytes=ctx.ws_bytes,
+                                    dL_dloss=g_loss.data_ptr(), dL_dinv_depths=d_inv.data_ptr(), dL_dposes=d_poses.data_ptr())
+        return (d_inv if ctx.needs_input_grad[0] else None, d_poses if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+
+
+def fused_photometric_loss(image: Tensor, ref_imgs: Tensor, inv_depths, K: Tensor, ref_Ks: Tensor, poses: Tensor, *,
+                           ssim_loss_weight: float = 0.85, smooth_loss_weight: float = 0.01, C1: float = 1e-4, C2: float = 9e-4,
+                           clip_loss: float = 0.5, automask_loss: bool = True, gamma: float = 0.85, return_choice: bool = False,
+                           padding_mode: str = "zeros", photometric_reduce_op: str = "min") -> PhotometricLoss:
+    """GGRt's ``MultiViewPhotometricDecayLoss.forward(image, ref_imgs, inv_depths, K, ref_Ks, poses)`` (``ggrt/loss/
+    photometric_loss.py``) as four HIP launches forward and two backward, whatever the numbers of iterations and views
+    (INTEGRATION.md §28; the arithmetic: ``GgrPhotometricLossPass`` in include/ggr_raster.h).  ``image`` [1,3,H,W] or [3,H,W];
+    ``ref_imgs`` [V,3,H,W]; ``inv_depths`` a list of n tensors [1,1,H,W], as the reference receives it, or one [n,1,H,W] tensor;
+    ``K`` [1,3,3]; ``ref_Ks`` [V,3,3]; ``poses`` [V,n,6], translation first, then the Euler angles of ``Pose.from_vec``; all float32 on
+    the GPU.  Returns ``PhotometricLoss(loss [1], photometric_loss [], smoothness_loss [], thresholds [n,C], choice [n,H,W] uint8 |
+    None)`` with C = 2V candidates per pixel (V without ``automask_loss``) in the reference's order: warped 0, unwarped 0, warped 1 …
+
+    ``loss`` is differentiable with respect to ``inv_depths`` and ``poses`` ONLY: the images and the intrinsics are data and get no
+    gradient (one that requires grad is refused).  The gradient reaches each pixel's winning candidate, and only where it was not
+    clamped; the thresholds ``mean + clip_loss·std`` are constants of the backward, as the reference's ``float()`` makes them, and
+    stay on the device: nothing synchronises with the host.  Ties of the minimum go to the LOWEST candidate index (with an identity
+    pose the warped image equals the unwarped one and the warped candidate wins).  ``photometric_loss`` is what the reference's
+    metric of that name holds — with the smoothness term on that is the whole loss, because the reference adds the term in place
+    to the tensor the metric shares its memory with.  ``clip_loss=0`` switches the clamp off, ``smooth_loss_weight=0`` skips the
+    smoothness term.  Two runs give the same bits.
+
+    Refused with a ValueError (use the reference's torch module for these): a batch other than 1; inverse-depth maps that are not at
+    the image's resolution; ``ssim_loss_weight <= 0`` (the reference then has 3 candidate planes per view); a ``padding_mode``
+    other than 'zeros' or a reduce other than 'min'; H or W below 2; V·n = 0; more than 16 candidates per pixel (V above 8 with the
+    auto-mask, above 16 without)."""
+    torch_route = "use the reference's torch module (MultiViewPhotometricDecayLoss) for that form"
+    if padding_mode != "zeros":
+        raise ValueError(f"fused_photometric_loss: padding_mode {padding_mode!r} is not 'zeros'; {torch_route}")
+    if photometric_reduce_op != "min":
+        raise ValueError(f"fused_photometric_loss: photometric_reduce_op {photometric_reduce_op!r} is not 'min'; {torch_route}")
+    if isinstance(inv_depths, (list, tuple)):
+        if len(inv_depths) == 0:
+            raise ValueError(f"fused_photometric_loss: no inverse-depth maps (V·n = 0); {torch_route}")
+        for d in inv_depths:
+            if not torch.is_tensor(d) or d.dim() != 4 or d.shape[0] != 1 or d.shape[1] != 1:
+                raise ValueError(f"fused_photometric_loss: an inverse-depth map is not a [1, 1, H, W] tensor (a batch other than 1?); {torch_route}")
+        if any(tuple(d.shape) != tuple(inv_depths[0].shape) for d in inv_depths):
+            raise ValueError(f"fused_photometric_loss: the inverse-depth maps are not all at one resolution; {torch_route}")
+        inv_depths = torch.cat(list(inv_depths), 0)
+    tensors = (("image", image), ("ref_imgs", ref_imgs), ("inv_depths", inv_depths), ("K", K), ("ref_Ks", ref_Ks), ("poses", poses))
+    for name, t in tensors:
+        if not torch.is_tensor(t):
+            raise ValueError(f"fused_photometric_loss: {name} is not a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"fused_photometric_loss: {name} is on {t.device}; the pass runs on the GPU only (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"fused_photometric_loss: {name} is {t.dtype}, not torch.float32")
+        if t.device != image.device:
+            raise RuntimeError("fused_photometric_loss: the inputs are not on one device")
+    for name, t in (("image", image), ("ref_imgs", ref_imgs), ("K", K), ("ref_Ks", ref_Ks)):
+        if t.requires_grad:
+            raise RuntimeError(f"fused_photometric_loss: {name} requires grad, but the images and intrinsics are data here: there is no gradient "
+                               "with respect to them (detach it)")
+    if image.dim() == 4:
+        if image.shape[0] != 1:
+            raise ValueError(f"fused_photometric_loss: image {tuple(image.shape)} has a batch other than 1; {torch_route}")
+        image = image[0]
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError(f"fused_photometric_loss: image {tuple(image.shape)} is neither [1, 3, H, W] nor [3, H, W]")
+    h, w = int(image.shape[1]), int(image.shape[2])
+    if h < 2 or w < 2:
+        raise ValueError(f"fused_photometric_loss: image {h} x {w} is below 2 x 2 (reflection padding needs two pixels); {torch_route}")
+    if ref_imgs.dim() != 4 or tuple(ref_imgs.shape[1:]) != (3, h, w):
+        raise ValueError(f"fused_photometric_loss: ref_imgs {tuple(ref_imgs.shape)} is not [V, 3, {h}, {w}] (a batch other than 1?); {torch_route}")
+    v = int(ref_imgs.shape[0])
+    if inv_depths.dim() != 4 or inv_depths.shape[1] != 1:
+        raise ValueError(f"fused_photometric_loss: inv_depths {tuple(inv_depths.shape)} is not [n, 1, H, W] (a batch other than 1?); {torch_route}")
+    n = int(inv_depths.shape[0])
+    if v * n == 0:
+        raise ValueError(f"fused_photometric_loss: {v} views x {n} iterations is nothing (V·n = 0); {torch_route}")
+    if tuple(inv_depths.shape[2:]) != (h, w):
+        raise ValueError(f"fused_photometric_loss: inv_depths {tuple(inv_depths.shape[2:])} is not at the image's resolution {h} x {w}; {torch_route}")
+    if tuple(K.shape) not in ((1, 3, 3), (3, 3)):
+        raise ValueError(f"fused_photometric_loss: K {tuple(K.shape)} is not [1, 3, 3] (a batch other than 1?); {torch_route}")
+    if tuple(ref_Ks.shape) != (v, 3, 3):
+        raise ValueError(f"fused_photometric_loss: ref_Ks {tuple(ref_Ks.shape)} is not [{v}, 3, 3]")
+    if tuple(poses.shape) != (v, n, 6):
+        raise ValueError(f"fused_photometric_loss: poses {tuple(poses.shape)} is not [{v}, {n}, 6]")
+    if not float(ssim_loss_weight) > 0.0:
+        raise ValueError(f"fused_photometric_loss: ssim_loss_weight {ssim_loss_weight} is not above 0 (the reference then keeps three L1 planes per "
+                         f"view); {torch_route}")
+    if float(ssim_loss_weight) > 1.0:
+        raise ValueError(f"fused_photometric_loss: ssim_loss_weight {ssim_loss_weight} is above 1")
+    for name, x in (("smooth_loss_weight", smooth_loss_weight), ("C1", C1), ("C2", C2), ("clip_loss", clip_loss), ("gamma", gamma)):
+        if not (float(x) >= 0.0 and float(x) < float("inf")):
+            raise ValueError(f"fused_photometric_loss: {name} {x} is negative or not finite")
+    c = v * (2 if automask_loss else 1)
+    if c > PHOTOMETRIC_MAX_CANDIDATES:
+        raise ValueError(f"fused_photometric_loss: {v} views make {c} candidates per pixel, more than the {PHOTOMETRIC_MAX_CANDIDATES} the pass is "
+                         f"compiled for; {torch_route}")
+    if n > 1024 or h > 16384 or w > 16384:
+        raise ValueError(f"fused_photometric_loss: {n} iterations at {h} x {w} is more than the pass takes (1024, 16384 x 16384); {torch_route}")
+    opts = dict(ssim_loss_weight=float(ssim_loss_weight), smooth_loss_weight=float(smooth_loss_weight), C1=float(C1), C2=float(C2),
+                clip_loss=float(clip_loss), gamma=float(gamma))
+    loss, photo, smooth, thresholds, choice = _FusedPhotometricLoss.apply(
+        inv_depths.reshape(n, h, w).contiguous(), poses.contiguous(), image.contiguous(), ref_imgs.contiguous(), K.reshape(3, 3).contiguous(),
+        ref_Ks.contiguous(), bool(automask_loss), opts)
+    return PhotometricLoss(loss=loss, photometric_loss=photo, smoothness_loss=smooth, thresholds=thresholds, choice=choice if return_choice else None)
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

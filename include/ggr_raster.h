@@ -1198,6 +1198,74 @@ int ggr_image_loss_window(int32_t window_size, float* out);
 int ggr_image_loss_forward(const GgrImageLossPass* pass, void* stream);
 int ggr_image_loss_backward(const GgrImageLossPass* pass, void* stream);
 
+/* GGRt's multi-view photometric loss (ggrt/loss/photometric_loss.py: MultiViewPhotometricDecayLoss.forward, batch 1, 'min' reduce,
+ * zeros padding, SSIM on) of one target image [3,H,W] against V reference images [V,3,H,W], for n inverse-depth maps [n,H,W] at the
+ * image's resolution and n poses per view [V,n,6] (translation, then the Euler angles x, y, z of R = Rx Ry Rz); K [3,3], ref_Ks
+ * [V,3,3]; everything float32 and dense.  C = automask ? 2V : V candidates per pixel, in the order warped 0, unwarped 0, warped 1 ...
+ *     warped(i,j)(q) = bilinear sample (zeros outside) of ref_imgs[j] at  ref_Ks[j] (R q' + t),  q' = Kinv (x, y, 1) / max(inv_depths[i](q), 1e-6)
+ *                      (depth 0 where the inverse depth is <= 0; the projected Z clamped at 1e-5; Kinv as Camera.Kinv builds it)
+ *     p(i,c)         = w * mean_ch clamp((1 - SSIM3x3)/2, 0, 1) + (1 - w) * mean_ch |x - image|,  x = warped(i,j) or ref_imgs[j],
+ *                      SSIM over 3 x 3 means with reflection padding, constants C1, C2
+ *     threshold(i,c) = mean p + clip_loss * std p (unbiased); p is clamped at it when clip_loss > 0
+ *     photometric    = sum_i gamma^(n-i-1) * mean_q min_c p(i,c)(q)          (ties of the minimum: the lowest c)
+ *     smoothness     = smooth_loss_weight / n * sum_i (mean |dx dn_i * exp(-mean_ch |dx image|)| + the same in y) / 2^i,
+ *                      dn_i = inv_depths[i] / max(mean inv_depths[i], 1e-6);   0 when smooth_loss_weight is 0
+ *     loss           = photometric + smoothness;   out_photometric receives the loss too: the reference's 'photometric_loss' metric
+ *                      is a detach() of the tensor that `loss += smoothness` then changes in place, and this pass reports what it reports
+ * ggr_photometric_loss_forward: four launches whatever n and V -> out_loss, out_photometric, out_smoothness [1], out_thresholds
+ *     [n,C], choice [n,H,W] (uint8: the winning candidate), and the state the backward reads: `planes` (the candidates before the
+ *     clip, ggr_photometric_loss_planes_bytes) and `state` [2n]; `workspace` (ggr_photometric_loss_workspace_bytes, 8-byte aligned)
+ *     is scratch of both directions.
+ * ggr_photometric_loss_backward: two launches; dL_dloss [1] and the forward's planes, out_thresholds, choice, state ->
+ *     dL_dinv_depths [n,H,W] and dL_dposes [V,n,6], both written whole.  The gradient reaches a pixel's winning candidate only, and
+ *     only where it was not clamped; the threshold is a constant; there is no gradient with respect to the images and intrinsics.
+ * No atomics and fixed orders of summation: two calls give the same bits.  Both calls allocate nothing, set no memory, read nothing
+ * back, are ordered on `stream`, do not synchronise and are hipGraph-capturable.  GGR_E_INVALID, before anything is enqueued, for a
+ * struct_size smaller than the struct, a nonzero reserved field, num_views or num_iters below 1 (num_iters above 1024), height or
+ * width outside 2..16384, automask other than 0 or 1, more than 16 candidates (V above 8 with the auto-mask, above 16 without),
+ * ssim_loss_weight not in (0, 1], a negative or non-finite smooth_loss_weight / clip_loss / gamma / C1 / C2, a NULL required pointer,
+ * a misaligned buffer, planes_bytes or workspace_bytes too small. */
+typedef struct GgrPhotometricLossPass {
+    int32_t struct_size;            /* sizeof(GgrPhotometricLossPass) */
+    int32_t reserved;               /* 0 */
+    int32_t num_views;              /* V >= 1 */
+    int32_t num_iters;              /* n: 1..1024 */
+    int32_t height;                 /* H: 2..16384 */
+    int32_t width;                  /* W: 2..16384 */
+    int32_t automask;               /* 1: the unwarped candidates take part (C = 2V); 0: C = V */
+    int32_t reserved2;              /* 0 */
+    float ssim_loss_weight;         /* w in (0, 1] */
+    float smooth_loss_weight;       /* >= 0; 0 skips the term */
+    float C1, C2;                   /* SSIM constants, >= 0 */
+    float clip_loss;                /* >= 0; 0 switches the clamp off (the thresholds are still written) */
+    float gamma;                    /* >= 0 */
+    const float* image;             /* [3,H,W] */
+    const float* ref_imgs;          /* [V,3,H,W] */
+    const float* inv_depths;        /* [n,H,W] */
+    const float* K;                 /* [3,3] */
+    const float* ref_Ks;            /* [V,3,3] */
+    const float* poses;             /* [V,n,6] */
+    float* planes;                  /* [n*V + (automask ? V : 0)][H,W]: written by the forward, read by the backward */
+    int64_t planes_bytes;
+    void* workspace;                /* scratch of workspace_bytes */
+    int64_t workspace_bytes;
+    float* out_thresholds;          /* [n,C]: written by the forward, read by the backward */
+    float* state;                   /* [2n]: written by the forward, read by the backward */
+    uint8_t* choice;                /* [n,H,W]: written by the forward, read by the backward */
+    float* out_loss;                /* forward: [1] */
+    float* out_photometric;         /* forward: [1] */
+    float* out_smoothness;          /* forward: [1] */
+    const float* dL_dloss;          /* backward: [1] */
+    float* dL_dinv_depths;          /* backward: [n,H,W], written whole */
+    float* dL_dposes;               /* backward: [V,n,6], written whole */
+} GgrPhotometricLossPass;
+
+/* bytes of GgrPhotometricLossPass.planes / .workspace, or -1 for sizes that the pass refuses */
+int64_t ggr_photometric_loss_planes_bytes(int32_t num_views, int32_t num_iters, int32_t height, int32_t width, int32_t automask);
+int64_t ggr_photometric_loss_workspace_bytes(int32_t num_views, int32_t num_iters, int32_t height, int32_t width, int32_t automask);
+int ggr_photometric_loss_forward(const GgrPhotometricLossPass* pass, void* stream);
+int ggr_photometric_loss_backward(const GgrPhotometricLossPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
