@@ -295,6 +295,21 @@ def photometric_loss_pass(**fields) -> GgrPhotometricLossPass:
     return GgrPhotometricLossPass(struct_size=C.sizeof(GgrPhotometricLossPass), **fields)
 
 
+class GgrWarpCostPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("num_views", C.c_int32), ("channels", C.c_int32),
+                ("height", C.c_int32), ("width", C.c_int32), ("reduce_mean", C.c_int32), ("fold_disp", C.c_int32),
+                ("scale_factor", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float), ("reserved2", C.c_int32),
+                ("fmap", C.c_void_p), ("fmaps_ref", C.c_void_p), ("inv_depth", C.c_void_p), ("K", C.c_void_p), ("ref_Ks", C.c_void_p),
+                ("poses", C.c_void_p), ("out_cost", C.c_void_p), ("out_cells", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("dL_dcost", C.c_void_p), ("dL_dfmap", C.c_void_p), ("dL_dfmaps_ref", C.c_void_p),
+                ("dL_dinv_depth", C.c_void_p), ("dL_dposes", C.c_void_p)]
+
+
+def warp_cost_pass(**fields) -> GgrWarpCostPass:
+    """The argument of ggr_warp_cost_forward / _backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrWarpCostPass(struct_size=C.sizeof(GgrWarpCostPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -395,6 +410,9 @@ SYMBOLS = [
     ("ggr_photometric_loss_workspace_bytes", C.c_int64, [C.c_int32] * 5),
     ("ggr_photometric_loss_forward", C.c_int, [C.POINTER(GgrPhotometricLossPass), C.c_void_p]),
     ("ggr_photometric_loss_backward", C.c_int, [C.POINTER(GgrPhotometricLossPass), C.c_void_p]),
+    ("ggr_warp_cost_workspace_bytes", C.c_int64, [C.c_int32] * 3),
+    ("ggr_warp_cost_forward", C.c_int, [C.POINTER(GgrWarpCostPass), C.c_void_p]),
+    ("ggr_warp_cost_backward", C.c_int, [C.POINTER(GgrWarpCostPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

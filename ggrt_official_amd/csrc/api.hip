@@ -21,6 +21,7 @@
 #include "epipolar_attn_enc.h"
 #include "image_loss.h"
 #include "photometric_loss.h"
+#include "warp_cost.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1905,6 +1906,95 @@ int ggr_photometric_loss_backward(const GgrPhotometricLossPass* lp, void* stream
     hipStream_t s = (hipStream_t)stream;
     ggr::launch_photo_loss_backward(a, s);
     KCHECK(false, s, "photometric_loss_backward");
+    return GGR_OK;
+}
+
+// ---- the feature-metric cost map (warp_cost.hip) -----------------------------------------------------------------------------------
+namespace {
+bool warp_cost_sizes_ok(int V, int h, int w) {
+    return V >= 1 && V <= ggr::kWarpMaxViews && h >= 2 && w >= 2 && h <= ggr::kWarpMaxSide && w <= ggr::kWarpMaxSide;
+}
+
+int warp_cost_pass_check(const GgrWarpCostPass* wp, bool backward, ggr::WarpCostArgs* a) {
+    if (!wp) return fail(GGR_E_INVALID, "null GgrWarpCostPass");
+    if (wp->struct_size < (int32_t)sizeof(GgrWarpCostPass))
+        return fail(GGR_E_INVALID, "GgrWarpCostPass.struct_size %d is smaller than the %d bytes of its fields", (int)wp->struct_size, (int)sizeof(GgrWarpCostPass));
+    if (wp->reserved != 0 || wp->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrWarpCostPass.reserved must be 0, not %d / %d", (int)wp->reserved, (int)wp->reserved2);
+    const int V = wp->num_views, C = wp->channels, h = wp->height, w = wp->width;
+    if (V < 1 || V > ggr::kWarpMaxViews) return fail(GGR_E_INVALID, "GgrWarpCostPass.num_views %d is outside 1..%d", V, ggr::kWarpMaxViews);
+    if (C < 1 || C > ggr::kWarpMaxChannels) return fail(GGR_E_INVALID, "GgrWarpCostPass.channels %d is outside 1..%d", C, ggr::kWarpMaxChannels);
+    if (h < 2 || h > ggr::kWarpMaxSide) return fail(GGR_E_INVALID, "GgrWarpCostPass.height %d is outside 2..%d", h, ggr::kWarpMaxSide);
+    if (w < 2 || w > ggr::kWarpMaxSide) return fail(GGR_E_INVALID, "GgrWarpCostPass.width %d is outside 2..%d", w, ggr::kWarpMaxSide);
+    if (wp->reduce_mean != 0 && wp->reduce_mean != 1) return fail(GGR_E_INVALID, "GgrWarpCostPass.reduce_mean must be 0 or 1, not %d", (int)wp->reduce_mean);
+    if (wp->fold_disp != 0 && wp->fold_disp != 1) return fail(GGR_E_INVALID, "GgrWarpCostPass.fold_disp must be 0 or 1, not %d", (int)wp->fold_disp);
+    if (!(wp->scale_factor > 0.f && wp->scale_factor <= 3.0e38f))
+        return fail(GGR_E_INVALID, "GgrWarpCostPass.scale_factor %g is not positive and finite", (double)wp->scale_factor);
+    if (wp->fold_disp && !(wp->min_depth > 0.f && wp->min_depth < wp->max_depth && wp->max_depth <= 3.0e38f))
+        return fail(GGR_E_INVALID, "GgrWarpCostPass.min_depth %g / .max_depth %g are not 0 < min_depth < max_depth < inf", (double)wp->min_depth, (double)wp->max_depth);
+    {
+        const void* in[] = {wp->fmap, wp->fmaps_ref, wp->inv_depth, wp->K, wp->ref_Ks, wp->poses};
+        const char* name[] = {"fmap", "fmaps_ref", "inv_depth", "K", "ref_Ks", "poses"};
+        for (int i = 0; i < 6; ++i)
+            if (!in[i]) return fail(GGR_E_INVALID, "GgrWarpCostPass.%s is NULL", name[i]);
+    }
+    if (!backward) {
+        if (!wp->out_cost) return fail(GGR_E_INVALID, "GgrWarpCostPass.out_cost is NULL");
+    } else {
+        if (!wp->dL_dcost) return fail(GGR_E_INVALID, "GgrWarpCostPass.dL_dcost is NULL");
+        if (!wp->dL_dfmap && !wp->dL_dfmaps_ref && !wp->dL_dinv_depth && !wp->dL_dposes)
+            return fail(GGR_E_INVALID, "GgrWarpCostPass: no output (dL_dfmap, dL_dfmaps_ref, dL_dinv_depth and dL_dposes are all NULL)");
+        if (wp->dL_dposes) {
+            const int64_t need = ggr::warp_cost_workspace_doubles(V, h, w) * (int64_t)sizeof(double);
+            if (!wp->workspace) return fail(GGR_E_INVALID, "GgrWarpCostPass.workspace is NULL");
+            if (wp->workspace_bytes < need)
+                return fail(GGR_E_INVALID, "GgrWarpCostPass.workspace_bytes %lld is smaller than the %lld bytes the pass needs", (long long)wp->workspace_bytes, (long long)need);
+            if (((uintptr_t)wp->workspace & 7u) != 0) return fail(GGR_E_INVALID, "GgrWarpCostPass.workspace is misaligned (it needs 8-byte alignment)");
+        }
+    }
+    const void* all[] = {wp->fmap, wp->fmaps_ref, wp->inv_depth, wp->K, wp->ref_Ks, wp->poses, wp->out_cost, wp->out_cells, wp->dL_dcost, wp->dL_dfmap,
+                         wp->dL_dfmaps_ref, wp->dL_dinv_depth, wp->dL_dposes};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrWarpCostPass: a buffer is misaligned (every array needs 4-byte alignment)");
+    a->V = V; a->C = C; a->h = h; a->w = w; a->mean = wp->reduce_mean; a->disp_on = wp->fold_disp;
+    a->scale = wp->scale_factor;
+    a->disp_a = 0.f; a->disp_b = 1.f;
+    if (wp->fold_disp) {        // disp_to_depth forms both numbers in double and the tensor arithmetic rounds them to float
+        const double lo = 1.0 / (double)wp->max_depth, hi = 1.0 / (double)wp->min_depth;
+        a->disp_a = (float)lo;
+        a->disp_b = (float)(hi - lo);
+    }
+    a->fmap = wp->fmap; a->fmaps_ref = wp->fmaps_ref; a->inv_depth = wp->inv_depth; a->K = wp->K; a->ref_Ks = wp->ref_Ks; a->poses = wp->poses;
+    a->cost = wp->out_cost; a->cells = backward ? nullptr : wp->out_cells; a->workspace = (double*)wp->workspace;
+    a->g_cost = wp->dL_dcost; a->g_fmap = wp->dL_dfmap; a->g_fmaps_ref = wp->dL_dfmaps_ref; a->g_inv = wp->dL_dinv_depth; a->g_poses = wp->dL_dposes;
+    return GGR_OK;
+}
+}  // namespace
+
+int64_t ggr_warp_cost_workspace_bytes(int32_t num_views, int32_t height, int32_t width) {
+    if (!warp_cost_sizes_ok(num_views, height, width)) return -1;
+    return ggr::warp_cost_workspace_doubles(num_views, height, width) * (int64_t)sizeof(double);
+}
+
+int ggr_warp_cost_forward(const GgrWarpCostPass* wp, void* stream) {
+    g_err[0] = 0;
+    ggr::WarpCostArgs a;
+    const int rc = warp_cost_pass_check(wp, false, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_warp_cost_forward(a, s);
+    KCHECK(false, s, "warp_cost_forward");
+    return GGR_OK;
+}
+
+int ggr_warp_cost_backward(const GgrWarpCostPass* wp, void* stream) {
+    g_err[0] = 0;
+    ggr::WarpCostArgs a;
+    const int rc = warp_cost_pass_check(wp, true, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_warp_cost_backward(a, s);
+    KCHECK(false, s, "warp_cost_backward");
     return GGR_OK;
 }
 

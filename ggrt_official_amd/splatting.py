@@ -1040,6 +1040,166 @@ def fused_photometric_loss(image: Tensor, ref_imgs: Tensor, inv_depths, K: Tenso
     return PhotometricLoss(loss=loss, photometric_loss=photo, smoothness_loss=smooth, thresholds=thresholds, choice=choice if return_choice else None)
 
 
+WARP_COST_MAX_VIEWS = 16     # kWarpMaxViews of csrc/warp_cost.h
+
+
+class _FusedWarpCost(torch.autograd.Function):
+    """ggr_warp_cost_forward / _backward (csrc/warp_cost.hip) behind autograd: float32 contiguous tensors on arrival (fmap [C,h,w],
+    fmaps_ref [V,C,h,w], inv_depth [h,w], poses [V,6], K [3,3], ref_Ks [V,3,3]) → cost [V,C,h,w] or [1,C,h,w], cells [V,h,w,3] or
+    None.  Only the inputs are saved: the backward recomputes the coordinates.  Every buffer comes from torch."""
+
+    @staticmethod
+    def _call(name, dev, dims, opts, **pointers):
+        v, c, h, w = dims
+        wp = _lib.warp_cost_pass(reserved=0, num_views=v, channels=c, height=h, width=w, reserved2=0, **opts, **pointers)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.load(), name)(C.byref(wp), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+    @staticmethod
+    def forward(ctx, fmap, fmaps_ref, inv_depth, poses, K, ref_Ks, want_cells, opts):
+        dev = fmap.device
+        v, c, h, w = fmaps_ref.shape
+        dims = (v, c, h, w)
+        cost = _image_loss_buffer((1 if opts["reduce_mean"] else v, c, h, w), dev)
+        cells = None
+        if want_cells:
+            cells = torch.full((v, h, w, 3), -(1 << 31), dtype=torch.int32, device=dev) if _IMAGE_LOSS_POISON else torch.empty((v, h, w, 3), dtype=torch.int32, device=dev)
+        _FusedWarpCost._call("ggr_warp_cost_forward", dev, dims, opts, fmap=fmap.data_ptr(), fmaps_ref=fmaps_ref.data_ptr(), inv_depth=inv_depth.data_ptr(),
+                             K=K.data_ptr(), ref_Ks=ref_Ks.data_ptr(), poses=poses.data_ptr(), out_cost=cost.data_ptr(),
+                             out_cells=cells.data_ptr() if want_cells else None)
+        ctx.dims, ctx.opts = dims, opts
+        ctx.save_for_backward(fmap, fmaps_ref, inv_depth, poses, K, ref_Ks)
+        ctx.set_materialize_grads(False)
+        if want_cells:
+            ctx.mark_non_differentiable(cells)
+        return cost, cells
+
+    @staticmethod
+    def backward(ctx, g_cost, _g_cells=None):
+        need = ctx.needs_input_grad[:4]
+        if g_cost is None or not any(need):
+            return (None,) * 8
+        fmap, fmaps_ref, inv_depth, poses, K, ref_Ks = ctx.saved_tensors
+        dev = fmap.device
+        v, c, h, w = ctx.dims
+        g_cost = g_cost.to(dtype=torch.float32).contiguous()
+        outs = [_image_loss_buffer(tuple(t.shape), dev) if n else None for t, n in zip((fmap, fmaps_ref, inv_depth, poses), need)]
+        if need[1]:         # the scatter adds into its output: a fill on the same stream, ahead of the launch
+            outs[1] = torch.full(tuple(fmaps_ref.shape), 0.0, dtype=torch.float32, device=dev)
+        ws_bytes = int(_lib.load().ggr_warp_cost_workspace_bytes(v, h, w)) if need[3] else 0
+        workspace = _image_loss_buffer((ws_bytes // 8,), dev, torch.float64) if need[3] else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _FusedWarpCost._call("ggr_warp_cost_backward", dev, ctx.dims, ctx.opts, fmap=fmap.data_ptr(), fmaps_ref=fmaps_ref.data_ptr(),
+                             inv_depth=inv_depth.data_ptr(), K=K.data_ptr(), ref_Ks=ref_Ks.data_ptr(), poses=poses.data_ptr(),
+                             workspace=ptr(workspace), workspace_bytes=ws_bytes, dL_dcost=g_cost.data_ptr(), dL_dfmap=ptr(outs[0]),
+                             dL_dfmaps_ref=ptr(outs[1]), dL_dinv_depth=ptr(outs[2]), dL_dposes=ptr(outs[3]))
+        return (*outs, None, None, None, None)
+
+
+def fused_warp_cost(fmap: Tensor, fmaps_ref, inv_depth: Tensor, K: Tensor, ref_Ks: Tensor, poses, *, scale_factor: float = 1.0 / 8,
+                    reduce: str = "mean", disp_range=None, return_cells: bool = False):
+    """The feature-metric cost map of GGRt's ``DepthPoseNet`` (``ggrt/depth_pose_network.py``) for all V views in one HIP launch forward
+    and two backward (the arithmetic: ``GgrWarpCostPass`` in include/ggr_raster.h).  ``reduce="mean"`` is
+    ``depth_cost_calc(inv_depth, fmap, fmaps_ref, poses, K, ref_Ks, scale_factor)`` → [1,C,h,w]; ``reduce="none"`` is
+    ``get_cost_each(poses[v], fmap, fmaps_ref[v], inv2depth(inv_depth), K, ref_Ks[v], scale_factor)`` for every v → [V,C,h,w].
+
+    ``fmap`` [1,C,h,w] or [C,h,w]; ``fmaps_ref`` [V,C,h,w] or a list of V tensors [1,C,h,w] (the reference's tuple from
+    ``torch.split``); ``inv_depth`` [1,1,h,w] at the maps' resolution; ``K`` [1,3,3] or [3,3] and ``ref_Ks`` [V,3,3], the
+    FULL-resolution intrinsics, scaled inside by ``scale_factor`` as ``Camera.scaled`` does; ``poses`` [V,6] or a list of V tensors
+    [1,6], translation first, then the Euler angles of ``Pose.from_vec``; all float32 on one GPU.  ``disp_range=(min_depth,
+    max_depth)`` folds ``disp_to_depth``: ``inv_depth`` is then the raw sigmoid disparity.  ``return_cells=True`` returns ``(cost,
+    cells)`` with ``cells`` [V,h,w,3] int32: the bilinear cell (floor u, floor v; (-2, -2) where no tap is reached) and the flag of a
+    clamped ``P.z``, as the kernel decided them.
+
+    Gradients reach ``fmap``, ``fmaps_ref``, ``inv_depth`` and ``poses``; one that does not require grad costs nothing.  The
+    intrinsics are data (one that requires grad is refused).  ``dL/dfmaps_ref`` is scattered with float atomics; every other output
+    is bit-reproducible.  No allocation inside, no host sync, graph-capturable.
+
+    Refused with a ValueError (use the reference's torch route, ``DepthPoseNet.get_cost_each``, for these): a dtype other than
+    float32; a CPU tensor; spatial sizes that differ between ``fmap``, ``fmaps_ref`` and ``inv_depth``; h or w below 2; V = 0 or above
+    16; a batch other than 1; ``scale_factor <= 0``; a ``reduce`` other than "mean" or "none"; a ``disp_range`` that is not
+    ``0 < min < max``."""
+    torch_route = "use the reference's torch route (DepthPoseNet.get_cost_each / depth_cost_calc) for that form"
+    if reduce not in ("mean", "none"):
+        raise ValueError(f"fused_warp_cost: reduce {reduce!r} is neither 'mean' nor 'none'; {torch_route}")
+    if not (isinstance(scale_factor, (int, float)) and float(scale_factor) > 0.0 and float(scale_factor) < float("inf")):
+        raise ValueError(f"fused_warp_cost: scale_factor {scale_factor!r} is not a positive finite number; {torch_route}")
+    if disp_range is not None:
+        try:
+            lo, hi = (float(x) for x in disp_range)
+        except (TypeError, ValueError):
+            raise ValueError(f"fused_warp_cost: disp_range {disp_range!r} is not a (min_depth, max_depth) pair; {torch_route}") from None
+        if not (0.0 < lo < hi < float("inf")):
+            raise ValueError(f"fused_warp_cost: disp_range {disp_range!r} is not 0 < min < max; {torch_route}")
+    for name, seq, tail in (("fmaps_ref", fmaps_ref, 4), ("poses", poses, 2)):
+        if isinstance(seq, (list, tuple)):
+            if len(seq) == 0:
+                raise ValueError(f"fused_warp_cost: {name} is empty (V = 0); {torch_route}")
+            for t in seq:
+                if not torch.is_tensor(t) or t.dim() != tail or t.shape[0] != 1:
+                    raise ValueError(f"fused_warp_cost: an entry of {name} is not a tensor with a leading 1 (a batch other than 1?); {torch_route}")
+            if any(tuple(t.shape) != tuple(seq[0].shape) or t.dtype != seq[0].dtype or t.device != seq[0].device for t in seq):
+                raise ValueError(f"fused_warp_cost: the entries of {name} differ in shape (spatial sizes), dtype or device; {torch_route}")
+    if isinstance(fmaps_ref, (list, tuple)):
+        fmaps_ref = torch.cat(list(fmaps_ref), 0)
+    if isinstance(poses, (list, tuple)):
+        poses = torch.cat(list(poses), 0)
+    tensors = (("fmap", fmap), ("fmaps_ref", fmaps_ref), ("inv_depth", inv_depth), ("K", K), ("ref_Ks", ref_Ks), ("poses", poses))
+    for name, t in tensors:
+        if not torch.is_tensor(t):
+            raise ValueError(f"fused_warp_cost: {name} is not a tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"fused_warp_cost: {name} is {t.dtype}, not torch.float32; {torch_route}")
+    for name, t in tensors:
+        if t.device.type != "cuda":
+            raise ValueError(f"fused_warp_cost: {name} is on {t.device}; the pass runs on the GPU only (there is no CPU fallback); {torch_route}")
+        if t.device != fmap.device:
+            raise ValueError(f"fused_warp_cost: {name} is on {t.device}, fmap on {fmap.device}: the inputs are not on one device")
+    for name, t in (("K", K), ("ref_Ks", ref_Ks)):
+        if t.requires_grad:
+            raise RuntimeError(f"fused_warp_cost: {name} requires grad, but the intrinsics are data here: there is no gradient with respect to "
+                               "them (detach it)")
+    if fmap.dim() == 4:
+        if fmap.shape[0] != 1:
+            raise ValueError(f"fused_warp_cost: fmap {tuple(fmap.shape)} has a batch other than 1; {torch_route}")
+        fmap = fmap[0]
+    if fmap.dim() != 3:
+        raise ValueError(f"fused_warp_cost: fmap {tuple(fmap.shape)} is neither [1, C, h, w] nor [C, h, w]")
+    c, h, w = (int(x) for x in fmap.shape)
+    if c < 1:
+        raise ValueError(f"fused_warp_cost: fmap {tuple(fmap.shape)} has no channels")
+    if h < 2 or w < 2:
+        raise ValueError(f"fused_warp_cost: fmap {h} x {w} is below 2 x 2 (align_corners divides by h - 1 and w - 1); {torch_route}")
+    if fmaps_ref.dim() != 4:
+        raise ValueError(f"fused_warp_cost: fmaps_ref {tuple(fmaps_ref.shape)} is not [V, C, h, w] (a batch other than 1?); {torch_route}")
+    v = int(fmaps_ref.shape[0])
+    if v == 0:
+        raise ValueError(f"fused_warp_cost: fmaps_ref {tuple(fmaps_ref.shape)} holds no view (V = 0); {torch_route}")
+    if v > WARP_COST_MAX_VIEWS:
+        raise ValueError(f"fused_warp_cost: fmaps_ref holds {v} views, more than the {WARP_COST_MAX_VIEWS} the pass is compiled for; {torch_route}")
+    if tuple(fmaps_ref.shape[1:]) != (c, h, w):
+        raise ValueError(f"fused_warp_cost: fmaps_ref {tuple(fmaps_ref.shape)} does not have fmap's channels and spatial sizes [{c}, {h}, {w}]; {torch_route}")
+    if inv_depth.dim() != 4 or inv_depth.shape[0] != 1 or inv_depth.shape[1] != 1:
+        raise ValueError(f"fused_warp_cost: inv_depth {tuple(inv_depth.shape)} is not [1, 1, h, w] (a batch other than 1?); {torch_route}")
+    if tuple(inv_depth.shape[2:]) != (h, w):
+        raise ValueError(f"fused_warp_cost: inv_depth {tuple(inv_depth.shape[2:])} does not have fmap's spatial sizes {h} x {w}; {torch_route}")
+    if h > 16384 or w > 16384 or c > 65536:
+        raise ValueError(f"fused_warp_cost: fmap [{c}, {h}, {w}] is more than the pass takes (65536 channels, 16384 x 16384); {torch_route}")
+    if tuple(K.shape) not in ((1, 3, 3), (3, 3)):
+        raise ValueError(f"fused_warp_cost: K {tuple(K.shape)} is not [1, 3, 3] (a batch other than 1?); {torch_route}")
+    if tuple(ref_Ks.shape) != (v, 3, 3):
+        raise ValueError(f"fused_warp_cost: ref_Ks {tuple(ref_Ks.shape)} is not [{v}, 3, 3]")
+    if tuple(poses.shape) != (v, 6):
+        raise ValueError(f"fused_warp_cost: poses {tuple(poses.shape)} is not [{v}, 6]")
+    opts = dict(reduce_mean=int(reduce == "mean"), fold_disp=int(disp_range is not None), scale_factor=float(scale_factor),
+                min_depth=float(disp_range[0]) if disp_range is not None else 0.0, max_depth=float(disp_range[1]) if disp_range is not None else 0.0)
+    cost, cells = _FusedWarpCost.apply(fmap.contiguous(), fmaps_ref.contiguous(), inv_depth.reshape(h, w).contiguous(), poses.contiguous(),
+                                       K.reshape(3, 3).contiguous(), ref_Ks.contiguous(), bool(return_cells), opts)
+    return (cost, cells) if return_cells else cost
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

@@ -1266,6 +1266,65 @@ int64_t ggr_photometric_loss_workspace_bytes(int32_t num_views, int32_t num_iter
 int ggr_photometric_loss_forward(const GgrPhotometricLossPass* pass, void* stream);
 int ggr_photometric_loss_backward(const GgrPhotometricLossPass* pass, void* stream);
 
+/* GGRt's feature-metric cost map (ggrt/depth_pose_network.py: DepthPoseNet.get_cost_each for V views at once, or depth_cost_calc,
+ * their mean; batch 1) of one target feature map fmap [C,h,w] against V reference maps fmaps_ref [V,C,h,w], for one inverse-depth
+ * map [h,w] at the maps' resolution and one pose per view [V,6] (translation, then the Euler angles x, y, z of R = Rx Ry Rz); K
+ * [3,3] and ref_Ks [V,3,3] are the FULL-resolution intrinsics; everything float32 and dense.  Per pixel (x, y) and view j:
+ *     d      = fold_disp ? 1/max_depth + (1/min_depth - 1/max_depth) * inv_depth : inv_depth          (disp_to_depth)
+ *     depth  = d <= 0 ? 0 : 1 / max(d, 1e-6)                                                          (inv2depth)
+ *     K', Kj' = the intrinsics scaled by s = scale_factor as scale_intrinsics does: fx s, fy s, (cx + 0.5) s - 0.5, (cy + 0.5) s - 0.5
+ *              (untouched when s is exactly 1); Kinv as Camera.Kinv builds it from K'
+ *     P      = Kj' (R (Kinv (x, y, 1) depth) + t),  Z = max(P.z, 1e-5),  (u, v) = (P.x / Z, P.y / Z)
+ *     cost_j = (fmap - bilinear sample (zeros outside, pixel coordinates) of fmaps_ref[j] at (u, v))^2
+ * out_cost is [V,C,h,w], or with reduce_mean [C,h,w], the mean over j in the order of j.
+ * ggr_warp_cost_forward: one launch -> out_cost and, where out_cells is not NULL, out_cells [V,h,w,3] int32: floor(u), floor(v)
+ *     as the kernel took them ((-2, -2) for a sample that reaches no tap) and 1 where P.z was clamped.
+ * ggr_warp_cost_backward: at most two launches; dL_dcost (as out_cost) -> dL_dfmap [C,h,w], dL_dfmaps_ref [V,C,h,w],
+ *     dL_dinv_depth [h,w], dL_dposes [V,6], each optional: a NULL one is skipped with its sums (at least one must be given;
+ *     `workspace`, ggr_warp_cost_workspace_bytes and 8-byte aligned, is needed only with dL_dposes).  dL_dfmap, dL_dinv_depth and
+ *     dL_dposes are written whole; dL_dfmaps_ref is ADDED to: the caller hands it in zeroed (or holding a gradient to add to).  The coordinates are recomputed by the forward's own operations, so the floor and clamp decisions are the
+ *     forward's.  A clamped P.z passes no gradient through Z, a tap outside the map receives none, and there is no gradient with
+ *     respect to the intrinsics.  dL_dfmaps_ref is a scatter with float atomics (equal up to the order of summation between
+ *     runs); every other output has a fixed order of summation: two calls give the same bits.
+ * Both calls allocate nothing, read nothing back, are ordered on `stream`, do not synchronise and are hipGraph-capturable.
+ * GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero reserved field, num_views
+ * outside 1..16, channels outside 1..65536, height or width outside 2..16384, reduce_mean or fold_disp other than 0 or 1, a
+ * scale_factor that is not positive and finite, with fold_disp depths that are not 0 < min_depth < max_depth < inf, a NULL
+ * required pointer, a backward without any output, a misaligned buffer, workspace_bytes too small. */
+typedef struct GgrWarpCostPass {
+    int32_t struct_size;            /* sizeof(GgrWarpCostPass) */
+    int32_t reserved;               /* 0 */
+    int32_t num_views;              /* V: 1..16 */
+    int32_t channels;               /* C: 1..65536 */
+    int32_t height;                 /* h: 2..16384 */
+    int32_t width;                  /* w: 2..16384 */
+    int32_t reduce_mean;            /* 1: out_cost is the mean over the views [C,h,w]; 0: [V,C,h,w] */
+    int32_t fold_disp;              /* 1: inv_depth is a raw disparity in [0, 1], mapped with min_depth and max_depth */
+    float scale_factor;             /* s > 0 */
+    float min_depth, max_depth;     /* with fold_disp: 0 < min_depth < max_depth */
+    int32_t reserved2;              /* 0 */
+    const float* fmap;              /* [C,h,w] */
+    const float* fmaps_ref;         /* [V,C,h,w] */
+    const float* inv_depth;         /* [h,w] */
+    const float* K;                 /* [3,3] */
+    const float* ref_Ks;            /* [V,3,3] */
+    const float* poses;             /* [V,6] */
+    float* out_cost;                /* forward: [V,C,h,w] or [C,h,w] */
+    int32_t* out_cells;             /* forward: [V,h,w,3] or NULL */
+    void* workspace;                /* backward with dL_dposes: scratch of workspace_bytes */
+    int64_t workspace_bytes;
+    const float* dL_dcost;          /* backward: as out_cost */
+    float* dL_dfmap;                /* backward: [C,h,w] or NULL */
+    float* dL_dfmaps_ref;           /* backward: [V,C,h,w], zero on entry, or NULL */
+    float* dL_dinv_depth;           /* backward: [h,w] or NULL */
+    float* dL_dposes;               /* backward: [V,6] or NULL */
+} GgrWarpCostPass;
+
+/* bytes of GgrWarpCostPass.workspace, or -1 for sizes that the pass refuses */
+int64_t ggr_warp_cost_workspace_bytes(int32_t num_views, int32_t height, int32_t width);
+int ggr_warp_cost_forward(const GgrWarpCostPass* pass, void* stream);
+int ggr_warp_cost_backward(const GgrWarpCostPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
