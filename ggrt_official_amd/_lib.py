@@ -310,6 +310,19 @@ def warp_cost_pass(**fields) -> GgrWarpCostPass:
     return GgrWarpCostPass(struct_size=C.sizeof(GgrWarpCostPass), **fields)
 
 
+class GgrUpsampleDepthPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("ratio", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32), ("fold_disp", C.c_int32), ("reserved2", C.c_int32),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("depth", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("dL_dout", C.c_void_p), ("dL_dmask", C.c_void_p),
+                ("dL_ddepth", C.c_void_p)]
+
+
+def upsample_depth_pass(**fields) -> GgrUpsampleDepthPass:
+    """The argument of ggr_upsample_depth_forward / _backward (include/ggr_raster.h), struct_size filled in."""
+    return GgrUpsampleDepthPass(struct_size=C.sizeof(GgrUpsampleDepthPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -413,6 +426,9 @@ SYMBOLS = [
     ("ggr_warp_cost_workspace_bytes", C.c_int64, [C.c_int32] * 3),
     ("ggr_warp_cost_forward", C.c_int, [C.POINTER(GgrWarpCostPass), C.c_void_p]),
     ("ggr_warp_cost_backward", C.c_int, [C.POINTER(GgrWarpCostPass), C.c_void_p]),
+    ("ggr_upsample_depth_workspace_bytes", C.c_int64, [C.c_int32] * 4),
+    ("ggr_upsample_depth_forward", C.c_int, [C.POINTER(GgrUpsampleDepthPass), C.c_void_p]),
+    ("ggr_upsample_depth_backward", C.c_int, [C.POINTER(GgrUpsampleDepthPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

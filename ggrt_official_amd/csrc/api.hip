@@ -22,6 +22,7 @@
 #include "image_loss.h"
 #include "photometric_loss.h"
 #include "warp_cost.h"
+#include "upsample_depth.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -1995,6 +1996,95 @@ int ggr_warp_cost_backward(const GgrWarpCostPass* wp, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     ggr::launch_warp_cost_backward(a, s);
     KCHECK(false, s, "warp_cost_backward");
+    return GGR_OK;
+}
+
+// ---- the convex depth upsampling (upsample_depth.hip) ------------------------------------------------------------------------------
+namespace {
+// the kernels index with 32-bit ints: the mask (the largest input) and `up` must each stay below 2^31 elements
+bool upsample_depth_sizes_ok(int64_t N, int64_t h, int64_t w, int64_t r) {
+    if (N < 1 || h < 1 || w < 1 || r < 1 || r > ggr::kUpsampleMaxRatio) return false;
+    if (h * r > ggr::kUpsampleMaxSide || w * r > ggr::kUpsampleMaxSide) return false;
+    const int64_t cells = h * w;                                    // (at most 2^32 here)
+    return N <= INT32_MAX / cells && N * cells <= INT32_MAX / (9 * r * r);
+}
+
+int upsample_depth_pass_check(const GgrUpsampleDepthPass* up, bool backward, ggr::UpsampleDepthArgs* a) {
+    if (!up) return fail(GGR_E_INVALID, "null GgrUpsampleDepthPass");
+    if (up->struct_size < (int32_t)sizeof(GgrUpsampleDepthPass))
+        return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.struct_size %d is smaller than the %d bytes of its fields", (int)up->struct_size, (int)sizeof(GgrUpsampleDepthPass));
+    if (up->reserved != 0 || up->reserved2 != 0)
+        return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.reserved must be 0, not %d / %d", (int)up->reserved, (int)up->reserved2);
+    const int N = up->batch, h = up->height, w = up->width, r = up->ratio, Ho = up->out_height, Wo = up->out_width;
+    if (r < 1 || r > ggr::kUpsampleMaxRatio) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.ratio %d is outside 1..%d", r, ggr::kUpsampleMaxRatio);
+    if (N < 1) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.batch %d is below 1", N);
+    if (h < 1) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.height %d is below 1", h);
+    if (w < 1) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.width %d is below 1", w);
+    if (Ho < 1) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.out_height %d is below 1", Ho);
+    if (Wo < 1) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.out_width %d is below 1", Wo);
+    if (up->fold_disp != 0 && up->fold_disp != 1) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.fold_disp must be 0 or 1, not %d", (int)up->fold_disp);
+    if (up->fold_disp && !(up->min_depth > 0.f && up->min_depth < up->max_depth && up->max_depth <= 3.0e38f))
+        return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.min_depth %g / .max_depth %g are not 0 < min_depth < max_depth < inf", (double)up->min_depth, (double)up->max_depth);
+    if (!upsample_depth_sizes_ok(N, h, w, r) || Ho > ggr::kUpsampleMaxSide || Wo > ggr::kUpsampleMaxSide || (int64_t)N * Ho > INT32_MAX / (int64_t)Wo)
+        return fail(GGR_E_INVALID, "GgrUpsampleDepthPass: batch %d, %d x %d cells at ratio %d to %d x %d is beyond 32-bit indexing (2^31 - 1 elements per array, "
+                    "sides of %d)", N, h, w, r, Ho, Wo, ggr::kUpsampleMaxSide);
+    if (!up->depth) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.depth is NULL");
+    if (!up->mask) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.mask is NULL");
+    if (!backward) {
+        if (!up->out) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.out is NULL");
+    } else {
+        if (!up->dL_dout) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.dL_dout is NULL");
+        if (!up->dL_dmask && !up->dL_ddepth) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass: no output (dL_dmask and dL_ddepth are both NULL)");
+    }
+    const int64_t need = ggr::upsample_depth_workspace_floats(N, h, w, r) * (int64_t)sizeof(float);
+    if (!up->workspace) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.workspace is NULL");
+    if (up->workspace_bytes < need)
+        return fail(GGR_E_INVALID, "GgrUpsampleDepthPass.workspace_bytes %lld is smaller than the %lld bytes the pass needs", (long long)up->workspace_bytes, (long long)need);
+    const void* all[] = {up->depth, up->mask, up->out, up->workspace, up->dL_dout, up->dL_dmask, up->dL_ddepth};
+    for (const void* p : all)
+        if (((uintptr_t)p & 3u) != 0) return fail(GGR_E_INVALID, "GgrUpsampleDepthPass: a buffer is misaligned (every array needs 4-byte alignment)");
+    a->N = N; a->h = h; a->w = w; a->r = r; a->Ho = Ho; a->Wo = Wo; a->disp_on = up->fold_disp;
+    a->disp_a = 0.f; a->disp_b = 1.f;
+    if (up->fold_disp) {        // disp_to_depth forms both numbers in double and the tensor arithmetic rounds them to float
+        const double lo = 1.0 / (double)up->max_depth, hi = 1.0 / (double)up->min_depth;
+        a->disp_a = (float)lo;
+        a->disp_b = (float)(hi - lo);
+    }
+    const int H = h * r, W = w * r;     // torch's area_pixel_compute_scale: (float)(in - 1) / (out - 1), 0 for one output index
+    a->sy = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+    a->sx = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+    a->inv_sy = (Ho > 1 && H > 1) ? (float)(Ho - 1) / (float)(H - 1) : 0.f;
+    a->inv_sx = (Wo > 1 && W > 1) ? (float)(Wo - 1) / (float)(W - 1) : 0.f;
+    a->depth = up->depth; a->mask = up->mask; a->out = up->out; a->workspace = (float*)up->workspace;
+    a->g_out = up->dL_dout; a->g_mask = up->dL_dmask; a->g_depth = up->dL_ddepth;
+    return GGR_OK;
+}
+}  // namespace
+
+int64_t ggr_upsample_depth_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t ratio) {
+    if (!upsample_depth_sizes_ok(batch, height, width, ratio)) return -1;
+    return ggr::upsample_depth_workspace_floats(batch, height, width, ratio) * (int64_t)sizeof(float);
+}
+
+int ggr_upsample_depth_forward(const GgrUpsampleDepthPass* up, void* stream) {
+    g_err[0] = 0;
+    ggr::UpsampleDepthArgs a;
+    const int rc = upsample_depth_pass_check(up, false, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_upsample_depth_forward(a, s);
+    KCHECK(false, s, "upsample_depth_forward");
+    return GGR_OK;
+}
+
+int ggr_upsample_depth_backward(const GgrUpsampleDepthPass* up, void* stream) {
+    g_err[0] = 0;
+    ggr::UpsampleDepthArgs a;
+    const int rc = upsample_depth_pass_check(up, true, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_upsample_depth_backward(a, s);
+    KCHECK(false, s, "upsample_depth_backward");
     return GGR_OK;
 }
 

@@ -1200,6 +1200,136 @@ def fused_warp_cost(fmap: Tensor, fmaps_ref, inv_depth: Tensor, K: Tensor, ref_K
     return (cost, cells) if return_cells else cost
 
 
+UPSAMPLE_DEPTH_MAX_RATIO = 8     # kUpsampleMaxRatio of csrc/upsample_depth.h
+
+
+class _FusedUpsampleDepth(torch.autograd.Function):
+    """ggr_upsample_depth_forward / _backward (csrc/upsample_depth.hip) behind autograd: float32 contiguous tensors on arrival (depth
+    [N,1,h,w], mask [N,9 r r,h,w]) → out [N,1,Ho,Wo].  Only the inputs are saved: the backward recomputes the softmax.  Every
+    buffer, the workspace included, comes from torch."""
+
+    @staticmethod
+    def _call(name, dev, dims, opts, **pointers):
+        n, h, w, r, ho, wo = dims
+        ws_bytes = int(_lib.load().ggr_upsample_depth_workspace_bytes(n, h, w, r))
+        if ws_bytes < 0:
+            raise ValueError(f"fused_upsample_depth: {n} maps of {h} x {w} cells at ratio {r} are more than the pass indexes (2^31 - 1 elements "
+                             "in the mask, sides of 65536); use the reference's torch route (DepthPoseNet.upsample_depth) for that form")
+        workspace = _image_loss_buffer((ws_bytes // 4,), dev)
+        up = _lib.upsample_depth_pass(reserved=0, batch=n, height=h, width=w, ratio=r, out_height=ho, out_width=wo, reserved2=0,
+                                      workspace=workspace.data_ptr(), workspace_bytes=ws_bytes, **opts, **pointers)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.load(), name)(C.byref(up), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+    @staticmethod
+    def forward(ctx, depth, mask, dims, opts):
+        dev = depth.device
+        n, h, w, r, ho, wo = dims
+        out = _image_loss_buffer((n, 1, ho, wo), dev)
+        _FusedUpsampleDepth._call("ggr_upsample_depth_forward", dev, dims, opts, depth=depth.data_ptr(), mask=mask.data_ptr(), out=out.data_ptr())
+        ctx.dims, ctx.opts = dims, opts
+        ctx.save_for_backward(depth, mask)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need = ctx.needs_input_grad[:2]
+        if g_out is None or not any(need):
+            return (None,) * 4
+        depth, mask = ctx.saved_tensors
+        dev = depth.device
+        g_out = g_out.to(dtype=torch.float32).contiguous()
+        g_depth = _image_loss_buffer(tuple(depth.shape), dev) if need[0] else None
+        g_mask = _image_loss_buffer(tuple(mask.shape), dev) if need[1] else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _FusedUpsampleDepth._call("ggr_upsample_depth_backward", dev, ctx.dims, ctx.opts, depth=depth.data_ptr(), mask=mask.data_ptr(),
+                                  dL_dout=g_out.data_ptr(), dL_dmask=ptr(g_mask), dL_ddepth=ptr(g_depth))
+        return g_depth, g_mask, None, None
+
+
+def fused_upsample_depth(depth, mask, *, ratio: int = 8, image_size=None, disp_range=None) -> Tensor:
+    """The convex depth upsampling of GGRt's ``DepthPoseNet`` (``ggrt/depth_pose_network.py``) in two HIP launches forward and two
+    backward (the arithmetic: ``GgrUpsampleDepthPass`` in include/ggr_raster.h):
+    ``upsample_depth(depth, mask, ratio, image_size)`` and, with ``disp_range=(min_depth, max_depth)``,
+    ``disp_to_depth(..., min_depth, max_depth)[0]`` of it → [N,1,Ho,Wo].
+
+    ``depth`` [N,1,h,w] or [N,h,w], ``mask`` [N,9·ratio²,h,w], or a list or tuple of such maps and as many masks, stacked along N:
+    the predictions of one ``DepthPoseNet.forward`` in one call.  ``image_size=None`` is (ratio·h, ratio·w), where the resize is the
+    identity.  All float32 on one GPU; inputs that are not contiguous (a ``channels_last`` mask) are made so.
+
+    Gradients reach ``depth`` and ``mask``; one that does not require grad costs nothing.  Both are gathers with a fixed order of
+    summation: two runs give the same bits.  No host sync, graph-capturable; the workspace (the size of ``up``) is a torch buffer.
+
+    Refused with a ValueError (use the reference's torch route, ``DepthPoseNet.upsample_depth``, for these): a dtype other than
+    float32; a CPU tensor; a mask whose channel count is not 9·ratio² or whose batch or spatial sizes differ from ``depth``'s; a
+    ``ratio`` outside 1..8; an ``image_size`` that is not two positive ints; a ``disp_range`` that is not ``0 < min < max``; an empty
+    map or list."""
+    torch_route = "use the reference's torch route (DepthPoseNet.upsample_depth) for that form"
+    if not (isinstance(ratio, int) and not isinstance(ratio, bool) and 1 <= ratio <= UPSAMPLE_DEPTH_MAX_RATIO):
+        raise ValueError(f"fused_upsample_depth: ratio {ratio!r} is not an int in 1..{UPSAMPLE_DEPTH_MAX_RATIO}; {torch_route}")
+    if disp_range is not None:
+        try:
+            lo, hi = (float(x) for x in disp_range)
+        except (TypeError, ValueError):
+            raise ValueError(f"fused_upsample_depth: disp_range {disp_range!r} is not a (min_depth, max_depth) pair; {torch_route}") from None
+        if not (0.0 < lo < hi < float("inf")):
+            raise ValueError(f"fused_upsample_depth: disp_range {disp_range!r} is not 0 < min < max; {torch_route}")
+    if isinstance(depth, (list, tuple)) != isinstance(mask, (list, tuple)):
+        raise ValueError(f"fused_upsample_depth: depth and mask must both be tensors or both be lists; {torch_route}")
+    if isinstance(depth, (list, tuple)):
+        if len(depth) == 0 or len(depth) != len(mask):
+            raise ValueError(f"fused_upsample_depth: depth holds {len(depth)} maps and mask {len(mask)}: the lists are empty or differ in length; {torch_route}")
+        depths, masks = list(depth), list(mask)
+    else:
+        depths, masks = [depth], [mask]
+    for name, seq in (("depth", depths), ("mask", masks)):
+        for t in seq:
+            if not torch.is_tensor(t):
+                raise ValueError(f"fused_upsample_depth: {name} is not a tensor (or a list of tensors)")
+            if t.dtype != torch.float32:
+                raise ValueError(f"fused_upsample_depth: {name} is {t.dtype}, not torch.float32; {torch_route}")
+    for name, seq in (("depth", depths), ("mask", masks)):
+        for t in seq:
+            if t.device.type != "cuda":
+                raise ValueError(f"fused_upsample_depth: {name} is on {t.device}; the pass runs on the GPU only (there is no CPU fallback); {torch_route}")
+            if t.device != depths[0].device:
+                raise ValueError(f"fused_upsample_depth: {name} is on {t.device}, depth on {depths[0].device}: the inputs are not on one device")
+    for k, d in enumerate(depths):
+        if d.dim() == 3:
+            depths[k] = d = d.unsqueeze(1)
+        if d.dim() != 4 or d.shape[1] != 1:
+            raise ValueError(f"fused_upsample_depth: depth {tuple(d.shape)} is neither [N, 1, h, w] nor [N, h, w]; {torch_route}")
+        m = masks[k]
+        if m.dim() != 4:
+            raise ValueError(f"fused_upsample_depth: mask {tuple(m.shape)} is not [N, 9 * ratio^2, h, w]; {torch_route}")
+        if m.shape[1] != 9 * ratio * ratio:
+            raise ValueError(f"fused_upsample_depth: mask has {m.shape[1]} channels, not 9 * ratio^2 = {9 * ratio * ratio} at ratio {ratio}; {torch_route}")
+        if m.shape[0] != d.shape[0] or tuple(m.shape[2:]) != tuple(d.shape[2:]):
+            raise ValueError(f"fused_upsample_depth: mask {tuple(m.shape)} does not have depth's batch and spatial sizes {tuple(d.shape)}; {torch_route}")
+        if tuple(d.shape[2:]) != tuple(depths[0].shape[2:]):
+            raise ValueError(f"fused_upsample_depth: the maps of the depth list differ in spatial sizes ({tuple(d.shape[2:])} and {tuple(depths[0].shape[2:])}); {torch_route}")
+    depth = depths[0] if len(depths) == 1 else torch.cat(depths, 0)
+    mask = masks[0] if len(masks) == 1 else torch.cat(masks, 0)
+    n, _, h, w = (int(x) for x in depth.shape)
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError(f"fused_upsample_depth: depth {tuple(depth.shape)} is empty; {torch_route}")
+    if image_size is None:
+        ho, wo = ratio * h, ratio * w
+    else:
+        try:
+            ho, wo = image_size
+        except (TypeError, ValueError):
+            raise ValueError(f"fused_upsample_depth: image_size {image_size!r} is not a (height, width) pair; {torch_route}") from None
+        if not all(isinstance(x, int) and not isinstance(x, bool) and x >= 1 for x in (ho, wo)):
+            raise ValueError(f"fused_upsample_depth: image_size {image_size!r} is not two positive ints; {torch_route}")
+    opts = dict(fold_disp=int(disp_range is not None), min_depth=float(disp_range[0]) if disp_range is not None else 0.0,
+                max_depth=float(disp_range[1]) if disp_range is not None else 0.0)
+    return _FusedUpsampleDepth.apply(depth.contiguous(), mask.contiguous(), (n, h, w, ratio, int(ho), int(wo)), opts)
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

@@ -1325,6 +1325,53 @@ int64_t ggr_warp_cost_workspace_bytes(int32_t num_views, int32_t height, int32_t
 int ggr_warp_cost_forward(const GgrWarpCostPass* pass, void* stream);
 int ggr_warp_cost_backward(const GgrWarpCostPass* pass, void* stream);
 
+/* GGRt's convex depth upsampling (ggrt/depth_pose_network.py: DepthPoseNet.upsample_depth, optionally followed by disp_to_depth) for
+ * a stacked batch: depth [N,h,w], mask [N,9 r r,h,w] -> out [N,Ho,Wo]; everything float32 and dense.  With r = ratio, mask channel
+ * c = k r r + i r + j holds tap k = ky 3 + kx of sub-row i and sub-column j:
+ *     p_k          = softmax over k of mask[n, k r r + i r + j, y, x]                       (the maximum subtracted first)
+ *     up[n, y r + i, x r + j] = sum_k p_k depth[n, y + ky - 1, x + kx - 1]                   (taps outside the map are zero)
+ *     out          = bilinear resize of up to (Ho, Wo) with align_corners: source = destination * (in - 1) / (out - 1) in float
+ *                    (scale 0 where out is 1), weights (1 - l, l), the neighbour clamped at the last row and column; at
+ *                    (Ho, Wo) = (r h, r w) it is `up` to the bit
+ *     out          = 1/max_depth + (1/min_depth - 1/max_depth) out                           with fold_disp (disp_to_depth)
+ * ggr_upsample_depth_forward: two launches (up into the workspace, then resize and affine map); one at the identity size.
+ * ggr_upsample_depth_backward: at most two launches; dL_dout (as out) -> dL_dmask [N,9 r r,h,w] and dL_ddepth [N,h,w], each
+ *     optional (at least one must be given).  Both are gathers written whole with a fixed order of summation: no atomics, nothing
+ *     to zero, two calls give the same bits.  The softmax is recomputed from the mask: the backward needs the inputs only.
+ * `workspace` (ggr_upsample_depth_workspace_bytes, 4-byte aligned) holds `up` forward and the per-tap sums [N,9,h,w] backward; its
+ * contents need not survive between the calls.  Both calls allocate nothing, read nothing back, are ordered on `stream`, do not
+ * synchronise and are hipGraph-capturable.
+ * GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero reserved field, ratio outside
+ * 1..8, batch, height, width, out_height or out_width below 1, fold_disp other than 0 or 1, with fold_disp depths that are not
+ * 0 < min_depth < max_depth < inf, a NULL required pointer, a backward without any output, a misaligned buffer, workspace_bytes too
+ * small, and sizes beyond 32-bit indexing: more than 2^31 - 1 elements in mask, up or out, or a side of up or out above 65536. */
+typedef struct GgrUpsampleDepthPass {
+    int32_t struct_size;            /* sizeof(GgrUpsampleDepthPass) */
+    int32_t reserved;               /* 0 */
+    int32_t batch;                  /* N >= 1 */
+    int32_t height;                 /* h >= 1 */
+    int32_t width;                  /* w >= 1 */
+    int32_t ratio;                  /* r: 1..8 */
+    int32_t out_height;             /* Ho >= 1 */
+    int32_t out_width;              /* Wo >= 1 */
+    int32_t fold_disp;              /* 1: the affine map of disp_to_depth with min_depth and max_depth follows the resize */
+    int32_t reserved2;              /* 0 */
+    float min_depth, max_depth;     /* with fold_disp: 0 < min_depth < max_depth */
+    const float* depth;             /* [N,h,w] */
+    const float* mask;              /* [N,9 r r,h,w] */
+    float* out;                     /* forward: [N,Ho,Wo] */
+    void* workspace;                /* scratch of workspace_bytes */
+    int64_t workspace_bytes;
+    const float* dL_dout;           /* backward: [N,Ho,Wo] */
+    float* dL_dmask;                /* backward: [N,9 r r,h,w] or NULL */
+    float* dL_ddepth;               /* backward: [N,h,w] or NULL */
+} GgrUpsampleDepthPass;
+
+/* bytes of GgrUpsampleDepthPass.workspace (4 N h w max(r r, 9)), or -1 for sizes that the pass refuses */
+int64_t ggr_upsample_depth_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t ratio);
+int ggr_upsample_depth_forward(const GgrUpsampleDepthPass* pass, void* stream);
+int ggr_upsample_depth_backward(const GgrUpsampleDepthPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
