@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import ggrt_official_amd.splatting as splatting
-from tests.test_upsample_depth_reference import DISP_RANGE, FULL_CASE, GPU_CASES
+from tests.test_upsample_depth_reference import DISP_RANGE, FULL_CASE, GPU_CASES, RESIZE_CASES
 from tests.upsample_depth_reference import INPUTS, make_upsample_case, run_upsample_depth
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +55,31 @@ def test_kernel_against_the_float64_restatement(name, disp_range):
     _check(name, make_upsample_case(N, h, w, r, size, seed), ratio=r, image_size=size, disp_range=disp_range)
 
 
+@pytest.mark.parametrize("disp_range", [None, DISP_RANGE], ids=["plain", "disp"])
+@pytest.mark.parametrize("name", sorted(RESIZE_CASES))
+def test_resize_regimes_against_the_float64_restatement(name, disp_range):
+    """The backward gather's destination window (`reach()`) and the tile seams at the regimes tests/test_upsample_depth_reference.py
+    names, plain and with the affine map.  The figures of the MI355X run: NOTES.md."""
+    N, h, w, r, size, seed = RESIZE_CASES[name]
+    _check(name, make_upsample_case(N, h, w, r, size, seed), ratio=r, image_size=size, disp_range=disp_range)
+
+
+@pytest.mark.parametrize("disp_range", [None, DISP_RANGE], ids=["plain", "disp"])
+def test_strong_down_leaves_the_unreached_pixels_exactly_zero(disp_range):
+    """48 x 88 -> 3 x 5: an `up` pixel that no destination reaches (or reaches with weight 0 only) has dL/dmask exactly 0.0 for its
+    nine taps, wherever the float32 restatement on the device — which forms the source coordinate as the kernel does — has.  `g` is
+    in [0.5, 1.5], so a reached pixel has a nonzero gradient.  (That more than half is zero is a condition on the input, checked on
+    the CPU too: tests/test_upsample_depth_reference.py.)"""
+    N, h, w, r, size, seed = RESIZE_CASES["strong_down"]
+    ref, t32, ker = _check("strong_down", make_upsample_case(N, h, w, r, size, seed), ratio=r, image_size=size, disp_range=disp_range)
+    zero32 = (t32["g_mask"].reshape(N, 9, r * r, h, w) == 0).all(1, keepdim=True).expand(N, 9, r * r, h, w)
+    got = ker["g_mask"].reshape(N, 9, r * r, h, w)
+    share32, share = float((t32["g_mask"] == 0).double().mean()), float((got == 0).double().mean())
+    print(f"strong_down: {share32:.4f} of t32's dL/dmask is exactly zero, {share:.4f} of the kernel's")
+    assert share32 > 0.5
+    assert bool((got[zero32] == 0).all()) and bool((got != 0).any())
+
+
 def test_ggrt_shape():
     N, h, w, r, size, seed = FULL_CASE
     _check("ggrt_shape", make_upsample_case(N, h, w, r, size, seed), ratio=r, image_size=size, disp_range=DISP_RANGE)
@@ -72,6 +97,39 @@ def test_a_one_hot_mask_returns_the_zero_padded_neighbour_to_the_bit(k):
     ky, kx = k // 3, k % 3
     want = F.pad(d, (1, 1, 1, 1))[:, :, ky:ky + h, kx:kx + w].repeat_interleave(r, 2).repeat_interleave(r, 3)
     assert torch.equal(out, want)
+
+
+@pytest.mark.parametrize("shape", [(5, 7, (3, 4)), (5, 7, (40, 9)), (1, 6, (5, 6)), (64, 3, (2, 3)), (9, 9, (9, 9))], ids=lambda s: f"{s[0]}x{s[1]}_to_{s[2][0]}x{s[2][1]}")
+def test_the_resize_is_a_linear_map_and_the_backward_its_adjoint(shape):
+    """r = 1 and a one-hot mask on the centre tap (200 against 0: exact, as the one-hot test shows): the pass is
+    F.interpolate(depth, size, bilinear, align_corners=True) and its transpose, so <out, g> = <depth, g_depth> up to rounding.  A
+    destination the gather drops or counts twice breaks the identity by far more.  No restatement here: the bar is the same defect
+    of float32 F.interpolate with autograd on the device, x 4, floor 1e-6; `out` against float64 F.interpolate under that bar too."""
+    h, w, size = shape
+    N, gen = 2, torch.Generator().manual_seed(950)
+    depth64 = 0.05 + 0.9 * torch.rand(N, 1, h, w, generator=gen, dtype=torch.float64)
+    g64 = torch.rand(N, 1, *size, generator=gen, dtype=torch.float64) + 0.5
+    depth, g = depth64.to(device=DEV, dtype=torch.float32).requires_grad_(True), g64.to(device=DEV, dtype=torch.float32)
+    mask = torch.zeros(N, 9, h, w, device=DEV)
+    mask[:, 4] = 200.0
+    out = _ker(depth, mask, ratio=1, image_size=size)
+    g_depth, = torch.autograd.grad((out * g).sum(), depth)
+    d32 = depth.detach().clone().requires_grad_(True)
+    out32 = F.interpolate(d32, size=size, mode="bilinear", align_corners=True)
+    g_depth32, = torch.autograd.grad((out32 * g).sum(), d32)
+    assert out.shape == out32.shape and not torch.isnan(out).any() and not torch.isnan(g_depth).any()
+
+    def defect(o, gd):
+        lhs, rhs = (o.detach().double() * g.double()).sum(), (depth.detach().double() * gd.double()).sum()
+        return float((lhs - rhs).abs() / lhs.abs())
+
+    e, e32 = defect(out, g_depth), defect(out32, g_depth32)
+    print(f"adjoint {h}x{w} -> {size}: kernel {e:.3e}, torch32 {e32:.3e}")
+    assert e <= max(4 * e32, 1e-6), (e, e32)
+    want = F.interpolate(depth64, size=size, mode="bilinear", align_corners=True)
+    v, v32 = _rel(out, want), _rel(out32, want)
+    print(f"resize {h}x{w} -> {size}: kernel {v:.3e}, torch32 {v32:.3e}")
+    assert v <= max(4 * v32, 1e-6), (v, v32)
 
 
 def test_an_all_zero_mask_is_the_zero_padded_box_mean():

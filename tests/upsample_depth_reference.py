@@ -28,11 +28,15 @@ def convex_upsample(depth, mask, ratio):
 
 
 def _axis(n_in, n_out, dtype, device):
-    scale = torch.tensor(float(n_in - 1), dtype=dtype, device=device) / (n_out - 1) if n_out > 1 else torch.zeros((), dtype=dtype, device=device)
-    src = scale * torch.arange(n_out, dtype=dtype, device=device)
-    i0 = src.floor().long().clamp(max=n_in - 1)
+    # the scale is a true division in `dtype` on the host, as torch (and the kernel's argument set-up) forms it: on the device a tensor
+    # divided by a number is multiplied by the reciprocal, and 55 * (1 / 55) is not 1 in float32
+    scale = torch.tensor(float(n_in - 1), dtype=dtype) / torch.tensor(float(n_out - 1), dtype=dtype) if n_out > 1 else torch.zeros((), dtype=dtype)
+    src = scale.to(device) * torch.arange(n_out, dtype=dtype, device=device)
+    # torch's CPU guard: the index is floorf of the coordinate whatever the dtype, the weight clamped to [0, 1].  Nothing in float32;
+    # in float64 a coordinate one ulp below an integer (49 * (55 / 49)) takes that integer with weight 0, not its lower neighbour
+    i0 = src.float().floor().long().clamp(max=n_in - 1)
     i1 = (i0 + 1).clamp(max=n_in - 1)
-    l1 = src - i0.to(dtype)
+    l1 = (src - i0.to(dtype)).clamp(0, 1)
     return i0, i1, 1 - l1, l1
 
 
