@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.environ.get("GGR_GOLDEN_OUT", HERE)
 sys.path.insert(0, ROOT)
 
-from tests.warp_cost_reference import INPUTS, make_warp_case  # noqa: E402
+from tests.warp_cost_reference import INPUTS, LARGE_ANGLES, make_warp_case  # noqa: E402
 
 
 class _AnythingMeta(type):
@@ -101,7 +101,8 @@ def main():
     #        name           V  C  h  w   seed  scale   options
     cases = [("v2c3_eighth", 2, 3, 9, 12, 800, 1.0 / 8, {}),
              ("v3c5_unit_far", 3, 5, 6, 7, 801, 1.0, dict(partly_out=1)),
-             ("v1c1_tiny", 1, 1, 2, 2, 802, 1.0 / 8, {})]
+             ("v1c1_tiny", 1, 1, 2, 2, 802, 1.0 / 8, {}),
+             ("v2c3_large_angles", 2, 3, 7, 10, 803, 1.0 / 8, dict(angles=LARGE_ANGLES[:2]))]
     for name, V, C, h, w, seed, scale, opts in cases:
         partly_out = opts.pop("partly_out", None)
         case = make_warp_case(V, C, h, w, seed, scale_factor=scale, **opts)

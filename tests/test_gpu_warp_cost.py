@@ -22,7 +22,8 @@ DEV = "cuda"
 # dL/dfmaps_ref between two runs, or two subsets of requires_grad: the same terms in another order.  An element receives a tap from
 # each pixel whose sample falls in one of its four cells — at these poses a handful, never more than 16 — so the orders differ by at
 # most 16 x 2^-24 of the sum of the terms' magnitudes, which the element's own scale bounds up to the cancellation between terms;
-# held against the tensor's maximum: 4e-6
+# held against the tensor's maximum: 4e-6.  This covers the moderate-pose cases only; where every sample lands in one cell
+# (test_scatter_into_one_cell) the bar is derived there, per element
 ORDER_BAR = 4e-6
 
 
@@ -155,6 +156,95 @@ def test_two_runs_give_the_same_bits():
         for k in ("cost", "cells", "g_fmap", "g_inv_depth", "g_poses"):
             assert torch.equal(a[k], b[k]), (form, k)
         assert float((a["g_fmaps_ref"] - b["g_fmaps_ref"]).abs().max()) <= ORDER_BAR * float(a["g_fmaps_ref"].abs().max())
+
+
+def _gpu_case(name):
+    V, C, h, w, seed, s, form, opts = GPU_CASES[name]
+    return make_warp_case(V, C, h, w, seed, scale_factor=s, **opts), dict(reduce=form, scale_factor=s, disp_range=opts.get("disp_range"))
+
+
+def _views(case, lo, hi):
+    return {k: (v[lo:hi] if k in ("fmaps_ref", "ref_Ks", "poses", "g_none") else v) for k, v in case.items()}
+
+
+def test_views_8_to_15_of_16_alone_give_the_same_bits():
+    """In the "none" form the views are independent: rows 8..15 of the tile's coordinate table and of the cameras, which only a
+    second trip of `tile_coordinates` fills, must hold what rows 0..7 hold when those views come alone."""
+    case, kw = _gpu_case("v16_none")
+    full = run_warp_cost(_ker, case, torch.float32, DEV, **kw)
+    half = run_warp_cost(_ker, _views(case, 8, 16), torch.float32, DEV, **kw)
+    for k in ("cost", "cells", "g_poses"):
+        assert tuple(half[k].shape[1:]) == tuple(full[k].shape[1:]) and half[k].shape[0] == 8
+        assert torch.equal(full[k][8:], half[k]), k
+    assert float(half["g_poses"].abs().amax(1).min()) > 0 and int((half["cells"][..., 0] >= 0).flatten(1).sum(1).min()) > 0
+
+
+def test_tiles_beyond_the_pose_kernels_first_trip():
+    """130 tiles: dL/dposes is the same bits twice, and with the upstream gradient zeroed on the first 64 tiles, so that nothing but
+    the pose kernel's second and third strided trips (the last a tail of two tiles, one of them partial) contributes, it still meets
+    the bar and is not zero."""
+    from tests.test_warp_cost_reference import upstream_beyond_tile_63
+    case, kw = _gpu_case("tiles130_tail")
+    a, b = (run_warp_cost(_ker, case, torch.float32, DEV, need=("poses",), **kw) for _ in range(2))
+    assert torch.equal(a["g_poses"], b["g_poses"]) and float(a["g_poses"].abs().amax(1).min()) > 0
+    masked = upstream_beyond_tile_63(case)
+    ref, t32, ker = _check("tiles130_tail_beyond_tile_63", masked, kw["reduce"], kw["scale_factor"])
+    assert float(ker["g_poses"].abs().amax(1).min()) > 0 and float(ker["g_fmap"].flatten(2)[..., :4096].abs().max()) == 0
+    assert not torch.equal(ker["g_poses"], a["g_poses"])
+
+
+def test_a_view_that_straddles_the_clamp_inside_a_tile():
+    case, kw = _gpu_case("straddle")
+    ref, t32, ker = _check("straddle", case, kw["reduce"], kw["scale_factor"])
+    flag = ker["cells"][0, ..., 2].cpu() == 1
+    assert bool(flag.flatten()[:64].any()) and bool((~flag).flatten()[:64].any()) and bool((ker["cells"][1, ..., 2] == 0).all())
+    # behind the camera Z is the constant 1e-5 and the sample leaves the frame: the cost is fmap^2 and view 0 adds nothing to the
+    # pixel's dL/dinv_depth, which the kernel sums over the views in a register in their order — view 1 alone gives the same bits
+    assert bool((ker["cells"][0, ..., :2].cpu()[flag] == -2).all())
+    assert torch.equal(ker["cost"][0].cpu()[:, flag], (case["fmap"].float()[0] ** 2)[:, flag])
+    alone = run_warp_cost(_ker, _views(case, 1, 2), torch.float32, DEV, **kw)
+    assert torch.equal(ker["g_inv_depth"][0, 0].cpu()[flag], alone["g_inv_depth"][0, 0].cpu()[flag])
+    assert float(alone["g_inv_depth"][0, 0].cpu()[flag].abs().max()) > 0
+    assert not torch.equal(ker["g_inv_depth"][0, 0].cpu()[~flag], alone["g_inv_depth"][0, 0].cpu()[~flag])
+
+
+@pytest.mark.parametrize("name", ["depth_column", "depth_column_disp"])
+def test_the_inverse_depth_gate_row_by_row(name):
+    """Every sample of the column is in frame (checked on the CPU), so a zero in dL/dinv_depth is the gate's doing: exactly zero where
+    the depth is a constant (d = 1e-7 under the clamp, 0, -1), not zero where it is 1 / d (just above 1e-6, and 1e3).  The row at the
+    gate itself (plain: d = 1e-6 exactly; folded: the same number as the row above it, see `_raw_disparity`) is held against the
+    restatement by `_check` like every other element, and takes the restatement's side."""
+    from tests.warp_cost_reference import DEPTH_COLUMN_VALUES
+    case, kw = _gpu_case(name)
+    x = GPU_CASES[name][7]["depth_column"]
+    ref, t32, ker = _check(name, case, kw["reduce"], kw["scale_factor"], kw["disp_range"])
+    col, col64 = ker["g_inv_depth"][0, 0, :, x].cpu(), ref["g_inv_depth"][0, 0, :, x]
+    print(f"{name}: dL/dinv_depth down the column, kernel {col.tolist()}, float64 {col64.tolist()}")
+    assert DEPTH_COLUMN_VALUES[0] == 1e-7 and DEPTH_COLUMN_VALUES[4:] == (0.0, -1.0) and DEPTH_COLUMN_VALUES[2:4] == (1.0000001e-6, 1e3)
+    assert bool((col[[0, 4, 5]] == 0).all()) and bool((col[[2, 3]] != 0).all())
+    assert (float(col[1]) != 0) == (float(col64[1]) != 0)
+    assert bool((ker["cells"][:, :, x, :2] != -2).all())
+
+
+def test_scatter_into_one_cell():
+    """Every pixel's sample lands in one cell: 128 float atomics on each of four addresses per channel.  The case is built so that
+    all terms of one element have the same sign; summing 128 such float32 terms in any order is within 127 x 2^-24 of the sum."""
+    from tests.test_warp_cost_reference import COLLAPSE_CASE
+    V, C, h, w, seed, s = COLLAPSE_CASE
+    case = make_warp_case(V, C, h, w, seed, scale_factor=s, collapse=True)
+    ref, t32, ker = _check("collapse", case, "none", s, keys=("cost", "g_fmap", "g_inv_depth", "g_poses"))
+    cells = ker["cells"].cpu()
+    assert bool((cells == torch.tensor([w // 2, h // 2, 0], dtype=torch.int32)).all())
+    hit = torch.zeros(h, w, dtype=torch.bool)
+    hit[h // 2: h // 2 + 2, w // 2: w // 2 + 2] = True
+    again = run_warp_cost(_ker, case, torch.float32, DEV, need=("fmaps_ref",), reduce="none", scale_factor=s)
+    g, g2, g32, g64 = (r["g_fmaps_ref"][0].double().cpu() for r in (ker, again, t32, ref))
+    assert not torch.isnan(g).any() and bool((g[:, hit] != 0).all()) and bool((g[:, ~hit] == 0).all()) and bool((g2[:, ~hit] == 0).all())
+    bar = torch.maximum(4 * (g32 - g64).abs(), 127 * 2.0 ** -24 * g64.abs())[:, hit]
+    e, e2 = (g - g64).abs()[:, hit], (g - g2).abs()[:, hit]
+    print(f"collapse g_fmaps_ref, per element over |ref|: kernel {(e / g64[:, hit].abs()).tolist()}, t32 {((g32 - g64).abs()[:, hit] / g64[:, hit].abs()).tolist()}, "
+          f"two runs {(e2 / g64[:, hit].abs()).tolist()}; 127 x 2^-24 = {127 * 2.0 ** -24:.3e}")
+    assert bool((e <= bar).all()) and bool((e2 <= bar).all())
 
 
 def test_list_inputs_and_noncontiguous_inputs():

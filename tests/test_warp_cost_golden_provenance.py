@@ -22,7 +22,7 @@ def test_warp_cost_fixtures_are_what_the_generator_produces(tmp_path):
                        stderr=subprocess.STDOUT, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-3000:]
     names = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "warp_cost_*.npz")))
-    assert len(names) == 3 and names == sorted(os.path.basename(f) for f in glob.glob(os.path.join(str(tmp_path), "warp_cost_*.npz")))
+    assert len(names) == 4 and names == sorted(os.path.basename(f) for f in glob.glob(os.path.join(str(tmp_path), "warp_cost_*.npz")))
     for n in names:
         a, b = np.load(os.path.join(GOLDEN, n), allow_pickle=False), np.load(os.path.join(str(tmp_path), n), allow_pickle=False)
         assert sorted(a.files) == sorted(b.files), n

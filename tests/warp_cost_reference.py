@@ -130,14 +130,55 @@ def _texture(xs, ys, g, channels, amp=0.4):
     return torch.stack(out)
 
 
+DEPTH_COLUMN_VALUES = (1e-7, 1e-6, 1.0000001e-6, 1e3, 0.0, -1.0)          # the rows of `depth_column` cycle through these inverse depths
+
+
+def depth_class(d):
+    """0 where the depth is the constant 0 (d <= 0), 1 where it is the clamp's constant (0 < d < 1e-6), 2 where it is 1 / d."""
+    return (d > 0).long() + (d >= 1e-6).long()
+
+
+def folded32(x, disp_range):
+    """disp_to_depth's affine map as float32 evaluates it (the restatement's own expression on a float32 tensor)."""
+    lo, hi = 1.0 / disp_range[1], 1.0 / disp_range[0]
+    return lo + (hi - lo) * x.to(torch.float32)
+
+
+def _raw_disparity(value, disp_range):
+    """The float32 number x for which d = lo + (hi - lo) x comes nearest to `value` among those (within 4096 float32 steps of the
+    exact raw disparity) for which float32 and float64 evaluate d alike: on `value`'s side of 0 and of the 1e-6 clamp in both, and,
+    where the depth is 1 / d, equal to 2^-22 of d.  Near lo the float32 fold moves in steps of about 2^-30, a thousandth of 1e-6:
+    for any other x the side of the gate, and the depth of 1e6 behind it, would be decided by rounding, differently in the two
+    precisions.  Needs a `disp_range` whose 1 / max and 1 / min - 1 / max are float32 numbers, such as (1, 128)."""
+    lo, hi = 1.0 / disp_range[1], 1.0 / disp_range[0]
+    want = int(depth_class(torch.tensor(value, dtype=torch.float64)))
+    x = torch.tensor([(value - lo) / (hi - lo)], dtype=torch.float64).to(torch.float32)
+    cands = (x.view(torch.int32) + torch.arange(-4096, 4097, dtype=torch.int32)).view(torch.float32)
+    d64, d32 = lo + (hi - lo) * cands.double(), folded32(cands, disp_range)
+    ok = (depth_class(d64) == want) & (depth_class(d32) == want)          # (float32 against the float32 1e-6, as the kernel compares)
+    if want == 2:
+        ok &= (d32.double() - d64).abs() <= 2.0 ** -22 * d64.abs()
+    assert bool(ok.any()), (value, disp_range)
+    return float(cands[ok][(d64[ok] - value).abs().argmin()])
+
+
 def make_warp_case(V, C, h, w, seed, scale_factor=1.0 / 8, identity=False, far_view=None, behind_view=None, nonpositive_block=False, disp_range=None,
-                   same_K=False):
+                   same_K=False, angles=None, straddle_view=None, depth_column=None, collapse=False):
     """Seeded float64 CPU inputs with smooth feature maps and moderate poses (shifts of one to two pixels, angles of a few
     milliradians), FULL-resolution intrinsics that differ per view, an inverse depth inside [0.35, 0.65] (with `disp_range` the raw
     disparity that maps there), and the upstream gradients `g_mean` [1,C,h,w] and `g_none` [V,C,h,w] the tests multiply the cost
     with.  `identity`: zero poses, equal power-of-two intrinsics and inverse depth 0.5, for which u = x and v = y exactly.
     `far_view`: that view's samples all leave the frame.  `behind_view`: that view's points lie behind its camera (P.z < 0).
-    `nonpositive_block`: a corner block of the inverse depth is 0 and negative."""
+    `nonpositive_block`: a corner block of the inverse depth is 0 and negative.
+    `angles` (V triples, radians): view j gets those Euler angles and the translation Xc - R Xc + t, with Xc the centre pixel lifted
+    with the scaled K to depth 2 and t the translation drawn otherwise: the centre stays put and the frame turns about it.
+    `straddle_view`: that view's t_z is minus a depth inside the map's range, so that P.z changes sign across the map, and its focal
+    length is STRADDLE_FOCAL of the others' (see there).
+    `depth_column`: that column of the inverse depth cycles through DEPTH_COLUMN_VALUES down its rows (with `disp_range`: through
+    the float32 raw disparities that `_raw_disparity` finds for them), and every t_z grows by 1 so that a point at depth 0 or 1e-3
+    still projects into the frame: what keeps its dL/dinv_depth at zero is the gate, not a sample that reaches nothing.
+    `collapse`: fmap = 2 (above every reference value, so fmap - warped > 0), inverse depth 1e4 (depth 1e-4, X about 0), t_z = 1 and
+    t_x, t_y such that Kr t / t_z = (w // 2 + 0.3, h // 2 + 0.6): every pixel samples that one cell."""
     g = torch.Generator().manual_seed(seed)
     s = float(scale_factor)
     ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
@@ -169,20 +210,46 @@ def make_warp_case(V, C, h, w, seed, scale_factor=1.0 / 8, identity=False, far_v
             t = t + torch.tensor([50.0, 0.0, 0.0], dtype=torch.float64)
         if behind_view is not None and j == behind_view:
             t = t + torch.tensor([0.0, 0.0, -6.0], dtype=torch.float64)
+        if angles is not None:
+            r = torch.tensor(angles[j], dtype=torch.float64)
+            Xc = 2.0 * torch.tensor([((w - 1) / 2.0 - cx_s) / f_s, ((h - 1) / 2.0 - cy_s) / f_s, 1.0], dtype=torch.float64)
+            t = Xc - euler_to_R(r[None])[0] @ Xc + t
+        if straddle_view is not None and j == straddle_view:
+            t[2] = -STRADDLE_DEPTH
+            ref_Ks[-1][0, 0] *= STRADDLE_FOCAL
+            ref_Ks[-1][1, 1] *= STRADDLE_FOCAL
+        if depth_column is not None:
+            t[2] = t[2] + 1.0
+        if collapse:
+            Kr = scaled_K(ref_Ks[-1], s)
+            t = torch.stack([(w // 2 + 0.3 - Kr[0, 2]) / Kr[0, 0], (h // 2 + 0.6 - Kr[1, 2]) / Kr[1, 1], torch.tensor(1.0, dtype=torch.float64)])
         poses.append(torch.cat([t, r]))
     d = torch.full((h, w), 0.5, dtype=torch.float64) if identity else 0.5 + 0.15 * torch.sin(xs / max(w, 4) * 3.1 + 0.4) * torch.cos(ys / max(h, 4) * 2.3)
     if nonpositive_block:
         d[: max(h // 3, 1), : max(w // 3, 1)] = 0.0
         d[0, 0] = -0.25
+    if depth_column is not None:
+        d[:, depth_column] = torch.tensor([DEPTH_COLUMN_VALUES[y % len(DEPTH_COLUMN_VALUES)] for y in range(h)], dtype=torch.float64)
+    if collapse:
+        fmap = torch.full_like(fmap, 2.0)
+        d = torch.full_like(d, 1e4)
     if disp_range is not None:
         lo, hi = 1.0 / disp_range[1], 1.0 / disp_range[0]
         d = (d - lo) / (hi - lo)
+        if depth_column is not None:
+            d[:, depth_column] = torch.tensor([_raw_disparity(DEPTH_COLUMN_VALUES[y % len(DEPTH_COLUMN_VALUES)], disp_range) for y in range(h)],
+                                              dtype=torch.float64)
     g3 = torch.Generator().manual_seed(seed * 104729 + 3)
     return dict(fmap=fmap, fmaps_ref=torch.stack(refs), inv_depth=d[None, None], K=K, ref_Ks=torch.stack(ref_Ks), poses=torch.stack(poses),
                 g_mean=torch.rand(1, C, h, w, generator=g3, dtype=torch.float64) + 0.5, g_none=torch.rand(V, C, h, w, generator=g3, dtype=torch.float64) + 0.5)
 
 
 INPUTS = ("fmap", "fmaps_ref", "inv_depth", "poses")
+STRADDLE_DEPTH = 1.7          # inside the depths of a case, 1 / 0.65 .. 1 / 0.35
+# The straddling camera sits INSIDE the scene: of the points in front of it only those in its frustum are sampled, and with the
+# other views' focal length that is a cone of about two pixels' width.  A quarter of the focal length opens it to a tenth of the map.
+STRADDLE_FOCAL = 0.25
+LARGE_ANGLES = ((0.5, -0.4, 0.7), (-0.35, 0.6, -0.9), (0.8, 0.3, 0.25))
 
 
 def run_warp_cost(route, case, dtype, device, decisions=None, need=INPUTS, reduce="mean", **opts):
@@ -204,6 +271,14 @@ def run_warp_cost(route, case, dtype, device, decisions=None, need=INPUTS, reduc
     for k in INPUTS:
         res["g_" + k] = t[k].grad
     return res
+
+
+def frame_masks(ref, h, w):
+    """[V,h,w] booleans of a restatement's run: the samples with all four taps live (0 <= u < w - 1 and 0 <= v < h - 1), and those in
+    the one-pixel border band, in frame with one or two live taps."""
+    u, v = ref["coords"][:, 0], ref["coords"][:, 1]
+    live4 = (u >= 0) & (u < w - 1) & (v >= 0) & (v < h - 1)
+    return live4, (u > -1) & (u < w) & (v > -1) & (v < h) & ~live4
 
 
 def near_border_share(ref64, ref32, h, w):
