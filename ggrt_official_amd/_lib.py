@@ -323,6 +323,19 @@ def upsample_depth_pass(**fields) -> GgrUpsampleDepthPass:
     return GgrUpsampleDepthPass(struct_size=C.sizeof(GgrUpsampleDepthPass), **fields)
 
 
+class GgrGruPass(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32)] + [(f, C.c_void_p) for f in (
+                    "a_zr_h", "a_zr_x", "h", "z", "r", "rh", "a_q_h", "a_q_x", "q", "out_h", "dL_dout_h", "dL_da_q", "dL_da_zr", "dL_dh_part",
+                    "dL_drh", "dL_dh")]
+
+
+def gru_pass(**fields) -> GgrGruPass:
+    """The argument of ggr_gru_gate_forward / _blend_forward / _blend_backward / _gate_backward (include/ggr_raster.h), struct_size
+    filled in."""
+    return GgrGruPass(struct_size=C.sizeof(GgrGruPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -429,6 +442,10 @@ SYMBOLS = [
     ("ggr_upsample_depth_workspace_bytes", C.c_int64, [C.c_int32] * 4),
     ("ggr_upsample_depth_forward", C.c_int, [C.POINTER(GgrUpsampleDepthPass), C.c_void_p]),
     ("ggr_upsample_depth_backward", C.c_int, [C.POINTER(GgrUpsampleDepthPass), C.c_void_p]),
+    ("ggr_gru_gate_forward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
+    ("ggr_gru_blend_forward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
+    ("ggr_gru_blend_backward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
+    ("ggr_gru_gate_backward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

@@ -23,6 +23,7 @@
 #include "photometric_loss.h"
 #include "warp_cost.h"
 #include "upsample_depth.h"
+#include "gru_gates.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -2087,6 +2088,75 @@ int ggr_upsample_depth_backward(const GgrUpsampleDepthPass* up, void* stream) {
     KCHECK(false, s, "upsample_depth_backward");
     return GGR_OK;
 }
+
+// ---- the ConvGRU gate math (gru_gates.hip) ------------------------------------------------------------------------------------------
+namespace {
+enum GruCall { GRU_GATE_FWD, GRU_BLEND_FWD, GRU_BLEND_BWD, GRU_GATE_BWD };
+
+int gru_pass_check(const GgrGruPass* gp, GruCall call, ggr::GruArgs* a) {
+    if (!gp) return fail(GGR_E_INVALID, "null GgrGruPass");
+    if (gp->struct_size < (int32_t)sizeof(GgrGruPass))
+        return fail(GGR_E_INVALID, "GgrGruPass.struct_size %d is smaller than the %d bytes of its fields", (int)gp->struct_size, (int)sizeof(GgrGruPass));
+    if (gp->reserved != 0) return fail(GGR_E_INVALID, "GgrGruPass.reserved must be 0, not %d", (int)gp->reserved);
+    const int N = gp->batch, Ch = gp->channels, H = gp->height, W = gp->width;
+    if (N < 1) return fail(GGR_E_INVALID, "GgrGruPass.batch %d is below 1", N);
+    if (Ch < 1) return fail(GGR_E_INVALID, "GgrGruPass.channels %d is below 1", Ch);
+    if (H < 1) return fail(GGR_E_INVALID, "GgrGruPass.height %d is below 1", H);
+    if (W < 1) return fail(GGR_E_INVALID, "GgrGruPass.width %d is below 1", W);
+    const int64_t M = (int64_t)Ch * H, lim = (int64_t)1 << 30;      // N M < 2^30: the [N,2Ch,H,W] arrays stay below 2^31 elements
+    if (M >= lim || M * W >= lim || M * W * N >= lim)
+        return fail(GGR_E_INVALID, "GgrGruPass: batch %d of %d x %d x %d is beyond 32-bit indexing (N 2 Ch H W must stay below 2^31)", N, Ch, H, W);
+    *a = ggr::GruArgs{};
+    a->N = N; a->M = (int)(M * W);
+#define GRU_NEED(field) if (!gp->field) return fail(GGR_E_INVALID, "GgrGruPass." #field " is NULL")
+    GRU_NEED(h);
+    switch (call) {
+    case GRU_GATE_FWD:
+        GRU_NEED(a_zr_h); GRU_NEED(z); GRU_NEED(r); GRU_NEED(rh);
+        a->a_zr_h = gp->a_zr_h; a->a_zr_x = gp->a_zr_x; a->z = gp->z; a->r = gp->r; a->rh = gp->rh;
+        break;
+    case GRU_BLEND_FWD:
+        GRU_NEED(a_q_h); GRU_NEED(z); GRU_NEED(q); GRU_NEED(out_h);
+        if (gp->out_h == gp->h) return fail(GGR_E_INVALID, "GgrGruPass.out_h is h itself: the blend does not run in place (the backward reads h)");
+        a->a_q_h = gp->a_q_h; a->a_q_x = gp->a_q_x; a->z = gp->z; a->q = gp->q; a->out_h = gp->out_h;
+        break;
+    case GRU_BLEND_BWD:
+        GRU_NEED(dL_dout_h); GRU_NEED(z); GRU_NEED(q);
+        if (!gp->dL_da_q && !gp->dL_da_zr && !gp->dL_dh_part) return fail(GGR_E_INVALID, "GgrGruPass: no output (dL_da_q, dL_da_zr and dL_dh_part are all NULL)");
+        a->g_out_h = gp->dL_dout_h; a->z = gp->z; a->q = gp->q; a->g_a_q = gp->dL_da_q; a->g_a_zr = gp->dL_da_zr; a->g_h_part = gp->dL_dh_part;
+        break;
+    case GRU_GATE_BWD:
+        GRU_NEED(dL_drh); GRU_NEED(r);
+        if (!gp->dL_da_zr && !gp->dL_dh) return fail(GGR_E_INVALID, "GgrGruPass: no output (dL_da_zr and dL_dh are both NULL)");
+        a->g_rh = gp->dL_drh; a->r = gp->r; a->g_a_zr = gp->dL_da_zr; a->g_h_part = gp->dL_dh_part; a->g_h = gp->dL_dh;
+        break;
+    }
+#undef GRU_NEED
+    a->h = gp->h;
+    const void* used[] = {a->a_zr_h, a->a_zr_x, a->h, a->z, a->r, a->rh, a->a_q_h, a->a_q_x, a->q, a->out_h, a->g_out_h, a->g_a_q, a->g_a_zr, a->g_h_part, a->g_rh, a->g_h};
+    uintptr_t bits = 0;
+    for (const void* p : used) bits |= (uintptr_t)p;
+    if ((bits & 3u) != 0) return fail(GGR_E_INVALID, "GgrGruPass: a buffer is misaligned (every array needs 4-byte alignment)");
+    a->vec = (a->M % 4 == 0 && (bits & 15u) == 0) ? 1 : 0;
+    return GGR_OK;
+}
+
+int gru_call(const GgrGruPass* gp, void* stream, GruCall call, void (*launch)(const ggr::GruArgs&, hipStream_t), const char* what) {
+    g_err[0] = 0;
+    ggr::GruArgs a;
+    const int rc = gru_pass_check(gp, call, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    launch(a, s);
+    KCHECK(false, s, what);
+    return GGR_OK;
+}
+}  // namespace
+
+int ggr_gru_gate_forward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_GATE_FWD, ggr::launch_gru_gate_forward, "gru_gate_forward"); }
+int ggr_gru_blend_forward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_BLEND_FWD, ggr::launch_gru_blend_forward, "gru_blend_forward"); }
+int ggr_gru_blend_backward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_BLEND_BWD, ggr::launch_gru_blend_backward, "gru_blend_backward"); }
+int ggr_gru_gate_backward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_GATE_BWD, ggr::launch_gru_gate_backward, "gru_gate_backward"); }
 
 // ---- the distortion pass (blend_dist.hip): the depth-distortion plane over a forward's lists, and its backward -----------------
 namespace {

@@ -1330,6 +1330,299 @@ def fused_upsample_depth(depth, mask, *, ratio: int = 8, image_size=None, disp_r
     return _FusedUpsampleDepth.apply(depth.contiguous(), mask.contiguous(), (n, h, w, ratio, int(ho), int(wo)), opts)
 
 
+_GRU_TORCH_ROUTE = "use the reference's torch route (SepConvGRU.forward / ConvGRU.forward of ggrt/optimizer.py) for that form"
+_GRU_DA_Z_MARK = "_ggr_gru_da_z"     # set on what _GruBlend.backward returns for z: the z half of a [N,2Ch,H,W] dL/da_zr buffer
+
+
+def _gru_call(name, dev, dims, **pointers):
+    n, ch, hh, ww = dims
+    gp = _lib.gru_pass(reserved=0, batch=n, channels=ch, height=hh, width=ww, **pointers)
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), name)(C.byref(gp), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed (code {rc}): {_lib.last_error()}")
+
+
+def _gru_ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+class _GruGate(torch.autograd.Function):
+    """ggr_gru_gate_forward / _backward (csrc/gru_gates.hip) behind autograd: a_zr_h, a_zr_x (or None) [N,2Ch,H,W] and h [N,Ch,H,W],
+    float32 contiguous on arrival → (z, rh).  Saves r and h.  The gradient that arrives for z is not dL/dz: it is what
+    `_GruBlend.backward` returns for its z, the z half of a dL/da_zr buffer whose r half this backward fills in place, so that the one
+    array serves as the gradient of both pre-activations.  Any other gradient for z (z used by something else than `gru_blend`, or by
+    two of them) is refused."""
+
+    @staticmethod
+    def forward(ctx, a_zr_h, a_zr_x, h):
+        dev, dims = h.device, tuple(int(v) for v in h.shape)
+        z, r, rh = (_image_loss_buffer(dims, dev) for _ in range(3))
+        _gru_call("ggr_gru_gate_forward", dev, dims, a_zr_h=a_zr_h.data_ptr(), a_zr_x=_gru_ptr(a_zr_x), h=h.data_ptr(), z=z.data_ptr(),
+                  r=r.data_ptr(), rh=rh.data_ptr())
+        ctx.dims = dims
+        ctx.save_for_backward(r, h)
+        ctx.set_materialize_grads(False)
+        return z, rh
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_rh):
+        need_a, need_h = ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if (g_z is None and g_rh is None) or not (need_a or need_h):
+            return None, None, None
+        r, h = ctx.saved_tensors
+        dev, (n, ch, hh, ww) = h.device, ctx.dims
+        g_a_zr = None
+        if need_a:
+            if g_z is None:             # the gate used alone: nothing reaches a_zr's z half
+                g_a_zr = _image_loss_buffer((n, 2 * ch, hh, ww), dev)
+                g_a_zr[:, :ch].zero_()
+            else:
+                g_a_zr = g_z._base if getattr(g_z, _GRU_DA_Z_MARK, False) else None
+                if (g_a_zr is None or tuple(g_a_zr.shape) != (n, 2 * ch, hh, ww) or not g_a_zr.is_contiguous() or g_a_zr.dtype != torch.float32
+                        or g_z.data_ptr() != g_a_zr.data_ptr()):
+                    raise RuntimeError("gru_gate: z is differentiable through one gru_blend only (its gradient slot carries dL/da_z, which "
+                                       "gru_blend's backward forms); another use of z received or added a gradient")
+        g_h = None
+        if g_rh is None:                # rh unused: r has no gradient, and h none through it
+            if g_a_zr is not None:
+                g_a_zr[:, ch:].zero_()
+        else:
+            g_rh = g_rh.to(dtype=torch.float32).contiguous()
+            g_h = _image_loss_buffer((n, ch, hh, ww), dev) if need_h else None
+            _gru_call("ggr_gru_gate_backward", dev, ctx.dims, dL_drh=g_rh.data_ptr(), r=r.data_ptr(), h=h.data_ptr(), dL_da_zr=_gru_ptr(g_a_zr),
+                      dL_dh=_gru_ptr(g_h))
+        return (g_a_zr if ctx.needs_input_grad[0] else None, g_a_zr if ctx.needs_input_grad[1] else None, g_h)
+
+
+class _GruBlend(torch.autograd.Function):
+    """ggr_gru_blend_forward / _backward behind autograd: a_q_h, a_q_x (or None), z, h [N,Ch,H,W] → h'.  Saves z, q and h.  What its
+    backward returns for z is dL/da_z (`_GruGate`)."""
+
+    @staticmethod
+    def forward(ctx, a_q_h, a_q_x, z, h):
+        dev, dims = h.device, tuple(int(v) for v in h.shape)
+        q, out = _image_loss_buffer(dims, dev), _image_loss_buffer(dims, dev)
+        _gru_call("ggr_gru_blend_forward", dev, dims, a_q_h=a_q_h.data_ptr(), a_q_x=_gru_ptr(a_q_x), z=z.data_ptr(), h=h.data_ptr(),
+                  q=q.data_ptr(), out_h=out.data_ptr())
+        ctx.dims = dims
+        ctx.save_for_backward(z, q, h)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        need_q = need[0] or need[1]
+        if g is None or not (need_q or need[2] or need[3]):
+            return None, None, None, None
+        z, q, h = ctx.saved_tensors
+        dev, (n, ch, hh, ww) = h.device, ctx.dims
+        g = g.to(dtype=torch.float32).contiguous()
+        g_a_q = _image_loss_buffer((n, ch, hh, ww), dev) if need_q else None
+        g_a_zr = _image_loss_buffer((n, 2 * ch, hh, ww), dev) if need[2] else None
+        g_h = _image_loss_buffer((n, ch, hh, ww), dev) if need[3] else None
+        _gru_call("ggr_gru_blend_backward", dev, ctx.dims, dL_dout_h=g.data_ptr(), z=z.data_ptr(), q=q.data_ptr(), h=h.data_ptr(),
+                  dL_da_q=_gru_ptr(g_a_q), dL_da_zr=_gru_ptr(g_a_zr), dL_dh_part=_gru_ptr(g_h))
+        g_z = None
+        if g_a_zr is not None:
+            g_z = g_a_zr[:, :ch]
+            setattr(g_z, _GRU_DA_Z_MARK, True)
+        return (g_a_q if need[0] else None, g_a_q if need[1] else None, g_z, g_h)
+
+
+def _gru_maps(fn, first, maps):
+    """The shared refusals of the GRU entry points: `maps` is [(name, tensor or None, channels or None)]; every tensor must be
+    float32, on one GPU, 4-D, and have `first`'s batch and spatial sizes (and the given channel count)."""
+    ref_name, ref = first
+    for name, t, _ in maps:
+        if t is not None and not torch.is_tensor(t):
+            raise ValueError(f"{fn}: {name} is not a tensor; {_GRU_TORCH_ROUTE}")
+    for name, t, _ in maps:
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{fn}: {name} is {t.dtype}, not torch.float32; {_GRU_TORCH_ROUTE}")
+    for name, t, _ in maps:
+        if t is not None and t.device.type != "cuda":
+            raise ValueError(f"{fn}: {name} is on {t.device}; the kernels run on the GPU only (there is no CPU fallback); {_GRU_TORCH_ROUTE}")
+    for name, t, _ in maps:
+        if t is not None and t.device != ref.device:
+            raise ValueError(f"{fn}: {name} is on {t.device}, {ref_name} on {ref.device}: the inputs are not on one device; {_GRU_TORCH_ROUTE}")
+    if ref.dim() != 4:
+        raise ValueError(f"{fn}: {ref_name} {tuple(ref.shape)} is not [N, C, H, W]; {_GRU_TORCH_ROUTE}")
+    if ref.shape[0] < 1 or ref.numel() == 0:
+        raise ValueError(f"{fn}: {ref_name} {tuple(ref.shape)} is empty; {_GRU_TORCH_ROUTE}")
+    for name, t, c in maps:
+        if t is None:
+            continue
+        if t.dim() != 4 or t.shape[0] != ref.shape[0] or tuple(t.shape[2:]) != tuple(ref.shape[2:]):
+            raise ValueError(f"{fn}: {name} {tuple(t.shape)} does not have {ref_name}'s batch and spatial sizes {tuple(ref.shape)}; {_GRU_TORCH_ROUTE}")
+        if c is not None and t.shape[1] != c:
+            raise ValueError(f"{fn}: {name} {tuple(t.shape)} has {t.shape[1]} channels, not {c}; {_GRU_TORCH_ROUTE}")
+    if 2 * ref.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: {ref_name} {tuple(ref.shape)} is more than the kernels index (N * 2 * Ch * H * W must stay below 2^31); {_GRU_TORCH_ROUTE}")
+
+
+def gru_gate(a_zr_h: Tensor, a_zr_x: Optional[Tensor], h: Tensor):
+    """The GRU's gates in one HIP launch each way (``GgrGruPass`` in include/ggr_raster.h): ``z = σ(a_zr_h[:, :Ch] + a_zr_x[:, :Ch])``,
+    ``r = σ(a_zr_h[:, Ch:] + a_zr_x[:, Ch:])``, ``rh = r·h`` → ``(z, rh)``.  ``a_zr_h`` and ``a_zr_x`` are the [N,2Ch,H,W]
+    pre-activations of the h-side and the x-side convolutions (``a_zr_x=None``: one convolution of a ``cat``), ``h`` [N,Ch,H,W].
+
+    ``z`` is made for :func:`gru_blend`: it is differentiable through exactly one ``gru_blend``, whose backward hands the gate
+    dL/da_z in z's gradient slot; a gradient from any other use of ``z`` raises a RuntimeError in the backward (``z.detach()`` is
+    free to use).  ``rh`` is an ordinary differentiable tensor."""
+    _gru_maps("gru_gate", ("h", h), [("h", h, None), ("a_zr_h", a_zr_h, 2 * h.shape[1] if torch.is_tensor(h) and h.dim() == 4 else None),
+                                     ("a_zr_x", a_zr_x, 2 * h.shape[1] if torch.is_tensor(h) and h.dim() == 4 else None)])
+    return _GruGate.apply(a_zr_h.contiguous(), a_zr_x.contiguous() if a_zr_x is not None else None, h.contiguous())
+
+
+def gru_blend(a_q_h: Tensor, a_q_x: Optional[Tensor], z: Tensor, h: Tensor) -> Tensor:
+    """The GRU's candidate and blend in one HIP launch each way: ``q = tanh(a_q_h + a_q_x)``, ``h' = (1 − z)·h + z·q`` → ``h'`` (a new
+    tensor).  All [N,Ch,H,W]; ``a_q_x=None``: no second addend.  ``z`` is :func:`gru_gate`'s (or any tensor that needs no gradient)."""
+    c = h.shape[1] if torch.is_tensor(h) and h.dim() == 4 else None
+    _gru_maps("gru_blend", ("h", h), [("h", h, None), ("a_q_h", a_q_h, c), ("a_q_x", a_q_x, c), ("z", z, c)])
+    return _GruBlend.apply(a_q_h.contiguous(), a_q_x.contiguous() if a_q_x is not None else None, z.contiguous(), h.contiguous())
+
+
+def fused_gru_half(h: Tensor, x: Tensor, w_zr_h: Tensor, w_zr_x: Tensor, b_zr: Optional[Tensor], w_q_h: Tensor, w_q_x: Tensor,
+                   b_q: Optional[Tensor], padding) -> Tensor:
+    """One half-step of GGRt's ``SepConvGRU`` (or the whole step of ``ConvGRU``, ``ggrt/optimizer.py``) with its three convolutions
+    over ``cat[h, x]`` split by input and its pointwise chain in two HIP launches each way (INTEGRATION.md §31)::
+
+        a_zr_h = conv(h, w_zr_h)      a_zr_x = conv(x, w_zr_x, b_zr)      a_q_x = conv(x, w_q_x, b_q)
+        z, rh  = gru_gate(a_zr_h, a_zr_x, h)
+        a_q_h  = conv(rh, w_q_h)
+        h'     = gru_blend(a_q_h, a_q_x, z, h)
+
+    ``h`` [N,Ch,H,W], ``x`` [N,Cx,H,W]; ``w_zr_h`` [2Ch,Ch,kh,kw] and ``w_zr_x`` [2Ch,Cx,kh,kw] hold the z rows, then the r rows;
+    ``w_q_h`` [Ch,Ch,kh,kw], ``w_q_x`` [Ch,Cx,kh,kw]; ``b_zr`` [2Ch] and ``b_q`` [Ch] (or None); ``padding`` = ((kh−1)/2, (kw−1)/2).
+    The same function of the same parameters as the reference's half-step up to float32 summation order.  The convolutions are
+    torch's; no ``cat`` and no [N,Ch+Cx,H,W] buffer is made.  Gradients reach every tensor argument that requires one.
+
+    Refused with a ValueError that names the argument: a dtype other than float32, a CPU tensor, inputs on different devices, ``h``
+    and ``x`` that differ in batch or spatial size, weights or biases whose shapes do not fit Ch / Cx / the padding, an empty batch."""
+    fn = "fused_gru_half"
+    tensors = [("h", h), ("x", x), ("w_zr_h", w_zr_h), ("w_zr_x", w_zr_x), ("b_zr", b_zr), ("w_q_h", w_q_h), ("w_q_x", w_q_x), ("b_q", b_q)]
+    for name, t in tensors:
+        if not (torch.is_tensor(t) or (t is None and name.startswith("b_"))):
+            raise ValueError(f"{fn}: {name} is not a tensor; {_GRU_TORCH_ROUTE}")
+    tensors = [(name, t) for name, t in tensors if t is not None]
+    for name, t in tensors:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{fn}: {name} is {t.dtype}, not torch.float32; {_GRU_TORCH_ROUTE}")
+    for name, t in tensors:
+        if t.device.type != "cuda":
+            raise ValueError(f"{fn}: {name} is on {t.device}; the kernels run on the GPU only (there is no CPU fallback); {_GRU_TORCH_ROUTE}")
+    for name, t in tensors:
+        if t.device != h.device:
+            raise ValueError(f"{fn}: {name} is on {t.device}, h on {h.device}: the inputs are not on one device; {_GRU_TORCH_ROUTE}")
+    if h.dim() != 4 or x.dim() != 4:
+        raise ValueError(f"{fn}: h {tuple(h.shape)} and x {tuple(x.shape)} are not [N, Ch, H, W] and [N, Cx, H, W]; {_GRU_TORCH_ROUTE}")
+    if h.shape[0] != x.shape[0] or tuple(h.shape[2:]) != tuple(x.shape[2:]):
+        raise ValueError(f"{fn}: x {tuple(x.shape)} does not have h's batch and spatial sizes {tuple(h.shape)}; {_GRU_TORCH_ROUTE}")
+    if h.numel() == 0 or x.numel() == 0:
+        raise ValueError(f"{fn}: h {tuple(h.shape)} or x {tuple(x.shape)} is empty; {_GRU_TORCH_ROUTE}")
+    try:
+        ph, pw = (int(v) for v in padding)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: padding {padding!r} is not a (rows, columns) pair; {_GRU_TORCH_ROUTE}") from None
+    ch, cx, kh, kw = int(h.shape[1]), int(x.shape[1]), 2 * ph + 1, 2 * pw + 1
+    if ph < 0 or pw < 0:
+        raise ValueError(f"{fn}: padding {padding!r} is negative; {_GRU_TORCH_ROUTE}")
+    for name, t, want in (("w_zr_h", w_zr_h, (2 * ch, ch, kh, kw)), ("w_zr_x", w_zr_x, (2 * ch, cx, kh, kw)), ("b_zr", b_zr, (2 * ch,)),
+                          ("w_q_h", w_q_h, (ch, ch, kh, kw)), ("w_q_x", w_q_x, (ch, cx, kh, kw)), ("b_q", b_q, (ch,))):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{fn}: {name} {tuple(t.shape)} is not {want} (Ch = {ch}, Cx = {cx}, padding {(ph, pw)}); {_GRU_TORCH_ROUTE}")
+    if 2 * h.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: h {tuple(h.shape)} is more than the kernels index (N * 2 * Ch * H * W must stay below 2^31); {_GRU_TORCH_ROUTE}")
+    h, x = h.contiguous(), x.contiguous()
+    conv = torch.nn.functional.conv2d
+    a_zr_h = conv(h, w_zr_h, None, padding=(ph, pw))
+    a_zr_x = conv(x, w_zr_x, b_zr, padding=(ph, pw))
+    a_q_x = conv(x, w_q_x, b_q, padding=(ph, pw))
+    z, rh = _GruGate.apply(a_zr_h.contiguous(), a_zr_x.contiguous(), h)
+    a_q_h = conv(rh, w_q_h, None, padding=(ph, pw))
+    return _GruBlend.apply(a_q_h.contiguous(), a_q_x.contiguous(), z, h)
+
+
+class _FusedGRU(nn.Module):
+    """The split parameters of a reference GRU and its forward through `fused_gru_half`.  HALVES lists (suffix of the reference's
+    module names, kernel shape, padding) in the order the reference applies them."""
+    HALVES: tuple = ()
+
+    def __init__(self, hidden_dim: int = 128, input_dim: int = 192 + 128):
+        super().__init__()
+        if not (isinstance(hidden_dim, int) and isinstance(input_dim, int) and hidden_dim >= 1 and input_dim >= 1):
+            raise ValueError(f"{type(self).__name__}: hidden_dim {hidden_dim!r} and input_dim {input_dim!r} are not positive ints")
+        self.hidden_dim, self.input_dim = hidden_dim, input_dim
+        ch, cx = hidden_dim, input_dim
+        init = {}
+        for s, (kh, kw), pad in self.HALVES:
+            for name, shape in (("w_zr_h", (2 * ch, ch, kh, kw)), ("w_zr_x", (2 * ch, cx, kh, kw)), ("b_zr", (2 * ch,)), ("w_q_h", (ch, ch, kh, kw)),
+                                ("w_q_x", (ch, cx, kh, kw)), ("b_q", (ch,))):
+                setattr(self, name + s, nn.Parameter(torch.empty(shape)))
+            for gate in "zrq":          # the reference's own initialisation: nn.Conv2d's, of the unsplit layer
+                conv = nn.Conv2d(ch + cx, ch, (kh, kw), padding=pad)
+                init[f"conv{gate}{s}.weight"], init[f"conv{gate}{s}.bias"] = conv.weight.detach(), conv.bias.detach()
+        self.load_reference_state_dict(init)
+
+    def _reference_keys(self):
+        return [f"conv{gate}{s}.{what}" for s, _, _ in self.HALVES for gate in "zrq" for what in ("weight", "bias")]
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd) -> None:
+        """Takes the parameters of the reference module (its ``state_dict()``: ``convz1.weight`` … ``convq2.bias`` for ``SepConvGRU``,
+        ``convz.weight`` … ``convq.bias`` for ``ConvGRU``), split by input channel and merged by gate.  Values are copied to the bit."""
+        keys, ch, cx = self._reference_keys(), self.hidden_dim, self.input_dim
+        if sorted(sd.keys()) != sorted(keys):
+            raise ValueError(f"{type(self).__name__}.load_reference_state_dict: expected the keys {keys}, got {sorted(sd.keys())}")
+        for s, (kh, kw), _ in self.HALVES:
+            for gate in "zrq":
+                w, b = sd[f"conv{gate}{s}.weight"], sd[f"conv{gate}{s}.bias"]
+                if tuple(w.shape) != (ch, ch + cx, kh, kw) or tuple(b.shape) != (ch,):
+                    raise ValueError(f"{type(self).__name__}.load_reference_state_dict: conv{gate}{s} has weight {tuple(w.shape)} and bias "
+                                     f"{tuple(b.shape)}, not {(ch, ch + cx, kh, kw)} and {(ch,)}")
+                rows = slice(ch, 2 * ch) if gate == "r" else slice(0, ch)
+                kind = "q" if gate == "q" else "zr"
+                getattr(self, f"w_{kind}_h{s}")[rows].copy_(w[:, :ch])
+                getattr(self, f"w_{kind}_x{s}")[rows].copy_(w[:, ch:])
+                getattr(self, f"b_{kind}{s}")[rows].copy_(b)
+
+    @torch.no_grad()
+    def reference_state_dict(self) -> dict:
+        """The parameters under the reference module's keys and shapes, in its order, bit for bit: ``load_state_dict`` of the
+        reference's ``SepConvGRU`` / ``ConvGRU`` takes it."""
+        ch, out = self.hidden_dim, {}
+        for s, _, _ in self.HALVES:
+            for gate in "zrq":
+                rows = slice(ch, 2 * ch) if gate == "r" else slice(0, ch)
+                kind = "q" if gate == "q" else "zr"
+                out[f"conv{gate}{s}.weight"] = torch.cat([getattr(self, f"w_{kind}_h{s}")[rows], getattr(self, f"w_{kind}_x{s}")[rows]], 1).clone()
+                out[f"conv{gate}{s}.bias"] = getattr(self, f"b_{kind}{s}")[rows].clone()
+        return out
+
+    def forward(self, h: Tensor, x: Tensor) -> Tensor:
+        if torch.is_tensor(x):
+            x = x.contiguous()
+        for s, _, pad in self.HALVES:
+            h = fused_gru_half(h, x, *(getattr(self, name + s) for name in ("w_zr_h", "w_zr_x", "b_zr", "w_q_h", "w_q_x", "b_q")), pad)
+        return h
+
+
+class FusedSepConvGRU(_FusedGRU):
+    """GGRt's ``SepConvGRU`` (``ggrt/optimizer.py:51-78``): a horizontal 1×5 half-step, then a vertical 5×1 one, each four torch
+    convolutions and two HIP launches.  Parameters per half (suffix 1, 2): ``w_zr_h``, ``w_zr_x``, ``b_zr``,
+    ``w_q_h``, ``w_q_x``, ``b_q``.  ``forward(h, x)`` as the reference's; checkpoints move both ways through
+    ``load_reference_state_dict`` / ``reference_state_dict``."""
+    HALVES = (("1", (1, 5), (0, 2)), ("2", (5, 1), (2, 0)))
+
+
+class FusedConvGRU(_FusedGRU):
+    """GGRt's ``ConvGRU`` (``ggrt/optimizer.py:33-48``): one 3×3 step, as `FusedSepConvGRU` (parameters without a suffix)."""
+    HALVES = (("", (3, 3), (1, 1)),)
+
+
 def boundary_arguments(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means,
                        gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities, scale_invariant=True,
                        use_sh=True, gaussian_scales=None, gaussian_rotations=None, scissor=None, sh_max_degree=None,

@@ -1372,6 +1372,64 @@ int64_t ggr_upsample_depth_workspace_bytes(int32_t batch, int32_t height, int32_
 int ggr_upsample_depth_forward(const GgrUpsampleDepthPass* pass, void* stream);
 int ggr_upsample_depth_backward(const GgrUpsampleDepthPass* pass, void* stream);
 
+/* The gate math of GGRt's SepConvGRU / ConvGRU (ggrt/optimizer.py:33-78) between its convolutions, on float32 dense NCHW maps.  The
+ * convolutions stay the host's.  With each of them split by input — the h side and the x side, which carries the bias — one
+ * half-step of the GRU is
+ *     a_zr_h = conv(h, w_zr_h)    a_zr_x = conv(x, w_zr_x, b_zr)    a_q_x = conv(x, w_q_x, b_q)
+ *     z, r, rh = GATE(a_zr_h, a_zr_x, h)       a_q_h = conv(rh, w_q_h)       q, h' = BLEND(a_q_h, a_q_x, z, h)
+ * Let M = Ch H W.  Element (n, c, p) of a [N,Ch,H,W] map is at n M + c HW + p; in the [N,2Ch,H,W] arrays (a_zr_h, a_zr_x, dL_da_zr)
+ * its z value is at n 2M + c HW + p and its r value M further on.
+ *   ggr_gru_gate_forward     z  = sigmoid(a_zr_h[z] + a_zr_x[z])     r = sigmoid(a_zr_h[r] + a_zr_x[r])     rh = r h
+ *                            reads a_zr_h, a_zr_x (or NULL: no second addend), h; writes z, r, rh whole.
+ *   ggr_gru_blend_forward    q  = tanh(a_q_h + a_q_x)                out_h = (1 - z) h + z q
+ *                            reads a_q_h, a_q_x (or NULL), z, h; writes q, out_h whole.  out_h must not be h.
+ *   ggr_gru_blend_backward   dL_da_q = g z (1 - q q)    dL_da_zr[z] = g (q - h) z (1 - z)    dL_dh_part = g (1 - z),   g = dL_dout_h
+ *                            reads dL_dout_h, z, q, h; writes dL_da_q (the gradient of both addends), the z half of dL_da_zr and
+ *                            dL_dh_part; each of the three may be NULL (not computed), not all.
+ *   ggr_gru_gate_backward    dL_da_zr[r] = dL_drh h r (1 - r)        dL_dh = dL_dh_part + dL_drh r
+ *                            reads dL_drh (the input gradient of the w_q_h convolution), r, h, dL_dh_part (or NULL: a gate used
+ *                            alone); writes the r half of dL_da_zr (the gradient of both addends) and dL_dh; either may be NULL, not
+ *                            both.  dL_dh excludes what the w_zr_h convolution's input gradient adds.
+ * sigmoid(a) is p or e p with e = exp(-|a|), p = 1 / (1 + e), and e taken as 0 below the smallest normal float; tanh(a) is
+ * sign(a) (-m / (2 + m)) with m = expm1(-2|a|).  Neither yields NaN or Inf for a finite a, and at |a| = 100 they are exactly 0, 1
+ * and +-1, so that z (1 - z), r (1 - r) and 1 - q q are exactly 0.
+ * One launch per call over N M elements, 16-byte accesses where M % 4 == 0 and every array is 16-byte aligned, 4-byte accesses
+ * otherwise.  Elementwise: no atomics, nothing to zero, two calls give the same bits, and an output may be the very array of an
+ * input of the same call (but out_h not h).  The calls allocate nothing, read nothing back, are ordered on `stream`, do not
+ * synchronise and are hipGraph-capturable.
+ * GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero reserved field, batch, channels,
+ * height or width below 1, N 2 M >= 2^31, a NULL required pointer, out_h == h, a backward call without any output, and a buffer
+ * that is not 4-byte aligned.  A pointer that a call does not name above is not looked at. */
+typedef struct GgrGruPass {
+    int32_t struct_size;            /* sizeof(GgrGruPass) */
+    int32_t reserved;               /* 0 */
+    int32_t batch;                  /* N >= 1 */
+    int32_t channels;               /* Ch >= 1: the hidden state's */
+    int32_t height;                 /* H >= 1 */
+    int32_t width;                  /* W >= 1 */
+    const float* a_zr_h;            /* [N,2Ch,H,W] */
+    const float* a_zr_x;            /* [N,2Ch,H,W] or NULL */
+    const float* h;                 /* [N,Ch,H,W]: every call reads it */
+    float* z;                       /* [N,Ch,H,W]: written by gate_forward, read by blend_forward and blend_backward */
+    float* r;                       /* [N,Ch,H,W]: written by gate_forward, read by gate_backward */
+    float* rh;                      /* [N,Ch,H,W]: written by gate_forward */
+    const float* a_q_h;             /* [N,Ch,H,W] */
+    const float* a_q_x;             /* [N,Ch,H,W] or NULL */
+    float* q;                       /* [N,Ch,H,W]: written by blend_forward, read by blend_backward */
+    float* out_h;                   /* [N,Ch,H,W]: h', written by blend_forward */
+    const float* dL_dout_h;         /* [N,Ch,H,W]: read by blend_backward */
+    float* dL_da_q;                 /* [N,Ch,H,W]: written by blend_backward, or NULL */
+    float* dL_da_zr;                /* [N,2Ch,H,W]: z half written by blend_backward, r half by gate_backward, or NULL */
+    float* dL_dh_part;              /* [N,Ch,H,W]: written by blend_backward, read by gate_backward, or NULL */
+    const float* dL_drh;            /* [N,Ch,H,W]: read by gate_backward */
+    float* dL_dh;                   /* [N,Ch,H,W]: written by gate_backward, or NULL */
+} GgrGruPass;
+
+int ggr_gru_gate_forward(const GgrGruPass* pass, void* stream);
+int ggr_gru_blend_forward(const GgrGruPass* pass, void* stream);
+int ggr_gru_blend_backward(const GgrGruPass* pass, void* stream);
+int ggr_gru_gate_backward(const GgrGruPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
