@@ -336,6 +336,20 @@ def gru_pass(**fields) -> GgrGruPass:
     return GgrGruPass(struct_size=C.sizeof(GgrGruPass), **fields)
 
 
+class GgrGruConvPass(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("struct_size", "reserved", "batch", "channels", "in_channels", "height", "width", "kernel_h", "kernel_w",
+                                         "epilogue", "out_channels")] + [(f, C.c_void_p) for f in (
+                    "a", "x", "w_h", "w_x", "bias", "h", "z", "rh", "out_h", "raw", "workspace")] + [("workspace_bytes", C.c_int64)]
+
+
+GRU_CONV_GATE, GRU_CONV_BLEND, GRU_CONV_RAW = 0, 1, 2
+
+
+def gru_conv_pass(**fields) -> GgrGruConvPass:
+    """The argument of ggr_gru_conv_forward / ggr_gru_conv_workspace_bytes (include/ggr_raster.h), struct_size filled in."""
+    return GgrGruConvPass(struct_size=C.sizeof(GgrGruConvPass), **fields)
+
+
 class GgrDistortionPass(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("geom_buffer", C.c_void_p),
                 ("image_buffer", C.c_void_p), ("binning_buffer", C.c_void_p), ("num_rendered", C.c_int64),
@@ -446,6 +460,8 @@ SYMBOLS = [
     ("ggr_gru_blend_forward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
     ("ggr_gru_blend_backward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
     ("ggr_gru_gate_backward", C.c_int, [C.POINTER(GgrGruPass), C.c_void_p]),
+    ("ggr_gru_conv_workspace_bytes", C.c_size_t, [C.POINTER(GgrGruConvPass)]),
+    ("ggr_gru_conv_forward", C.c_int, [C.POINTER(GgrGruConvPass), C.c_void_p]),
     ("ggr_distortion_forward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_distortion_backward", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrDistortionPass), C.c_void_p]),
     ("ggr_means2d_absgrad", C.c_int, [C.POINTER(GgrSettings), C.POINTER(GgrViews), C.POINTER(GgrAbsgradPass), C.c_void_p]),

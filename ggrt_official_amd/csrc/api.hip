@@ -24,6 +24,7 @@
 #include "warp_cost.h"
 #include "upsample_depth.h"
 #include "gru_gates.h"
+#include "gru_conv.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -2157,6 +2158,78 @@ int ggr_gru_gate_forward(const GgrGruPass* gp, void* stream) { return gru_call(g
 int ggr_gru_blend_forward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_BLEND_FWD, ggr::launch_gru_blend_forward, "gru_blend_forward"); }
 int ggr_gru_blend_backward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_BLEND_BWD, ggr::launch_gru_blend_backward, "gru_blend_backward"); }
 int ggr_gru_gate_backward(const GgrGruPass* gp, void* stream) { return gru_call(gp, stream, GRU_GATE_BWD, ggr::launch_gru_gate_backward, "gru_gate_backward"); }
+
+// ---- the ConvGRU half-step's convolutions with the gate math on the accumulators (gru_conv.hip) --------------------------------------
+namespace {
+int gru_conv_pass_check(const GgrGruConvPass* cp, ggr::GruConvArgs* a) {
+    if (!cp) return fail(GGR_E_INVALID, "null GgrGruConvPass");
+    if (cp->struct_size < (int32_t)sizeof(GgrGruConvPass))
+        return fail(GGR_E_INVALID, "GgrGruConvPass.struct_size %d is smaller than the %d bytes of its fields", (int)cp->struct_size, (int)sizeof(GgrGruConvPass));
+    if (cp->reserved != 0) return fail(GGR_E_INVALID, "GgrGruConvPass.reserved must be 0, not %d", (int)cp->reserved);
+    const int N = cp->batch, Ch = cp->channels, Cx = cp->in_channels, H = cp->height, W = cp->width, kh = cp->kernel_h, kw = cp->kernel_w;
+    if (N < 1) return fail(GGR_E_INVALID, "GgrGruConvPass.batch %d is below 1", N);
+    if (Ch < 1) return fail(GGR_E_INVALID, "GgrGruConvPass.channels %d is below 1", Ch);
+    if (Cx < 1) return fail(GGR_E_INVALID, "GgrGruConvPass.in_channels %d is below 1", Cx);
+    if (H < 1) return fail(GGR_E_INVALID, "GgrGruConvPass.height %d is below 1", H);
+    if (W < 1) return fail(GGR_E_INVALID, "GgrGruConvPass.width %d is below 1", W);
+    if (kh < 1 || kh > ggr::kGruConvMaxSide || kh % 2 == 0) return fail(GGR_E_INVALID, "GgrGruConvPass.kernel_h %d is not 1, 3 or 5", kh);
+    if (kw < 1 || kw > ggr::kGruConvMaxSide || kw % 2 == 0) return fail(GGR_E_INVALID, "GgrGruConvPass.kernel_w %d is not 1, 3 or 5", kw);
+    const int epi = cp->epilogue;
+    if (epi != GGR_GRU_CONV_GATE && epi != GGR_GRU_CONV_BLEND && epi != GGR_GRU_CONV_RAW)
+        return fail(GGR_E_INVALID, "GgrGruConvPass.epilogue %d is none of GGR_GRU_CONV_GATE, _BLEND, _RAW", epi);
+    if (epi == GGR_GRU_CONV_RAW && cp->out_channels < 1) return fail(GGR_E_INVALID, "GgrGruConvPass.out_channels %d is below 1", (int)cp->out_channels);
+    const int64_t lim = (int64_t)1 << 31, half = lim / 2, M = (int64_t)Ch * H;      // N M W < 2^30, as for GgrGruPass: no product overflows on the way
+    if (M >= half || M * W >= half || M * W * N >= half)
+        return fail(GGR_E_INVALID, "GgrGruConvPass: batch %d of %d x %d x %d is beyond 32-bit indexing (N 2 Ch H W must stay below 2^31)", N, Ch, H, W);
+    const int64_t P = (int64_t)N * H * W, Cout = epi == GGR_GRU_CONV_GATE ? 2 * (int64_t)Ch : epi == GGR_GRU_CONV_BLEND ? Ch : cp->out_channels;
+    const int64_t Cmax = Cx > Cout ? Cx : Cout, Kmax = (int64_t)(Ch > Cx ? Ch : Cx) * kh * kw;
+    if (Cmax * P >= lim || Kmax >= lim - 64)
+        return fail(GGR_E_INVALID, "GgrGruConvPass: batch %d, %d + %d -> %lld channels of %d x %d is beyond 32-bit indexing (every array must stay below 2^31 elements)",
+                    N, Ch, Cx, (long long)Cout, H, W);
+    *a = ggr::GruConvArgs{};
+    a->N = N; a->Ch = Ch; a->Cx = Cx; a->H = H; a->W = W; a->KH = kh; a->KW = kw; a->Cout = (int)Cout;
+    a->epilogue = epi == GGR_GRU_CONV_GATE ? ggr::kGruConvGate : epi == GGR_GRU_CONV_BLEND ? ggr::kGruConvBlend : ggr::kGruConvRaw;
+#define GRUC_NEED(field) if (!cp->field) return fail(GGR_E_INVALID, "GgrGruConvPass." #field " is NULL")
+    GRUC_NEED(a); GRUC_NEED(x); GRUC_NEED(w_h); GRUC_NEED(w_x);
+    a->a = cp->a; a->x = cp->x; a->w_h = cp->w_h; a->w_x = cp->w_x; a->bias = cp->bias;
+    if (epi == GGR_GRU_CONV_GATE) {
+        GRUC_NEED(h); GRUC_NEED(z); GRUC_NEED(rh);
+        a->h = cp->h; a->z = cp->z; a->rh = cp->rh;
+    } else if (epi == GGR_GRU_CONV_BLEND) {
+        GRUC_NEED(h); GRUC_NEED(z); GRUC_NEED(out_h);
+        if (cp->out_h == cp->h) return fail(GGR_E_INVALID, "GgrGruConvPass.out_h is h itself: the blend does not run in place");
+        a->h = cp->h; a->z = cp->z; a->out_h = cp->out_h;
+    } else {
+        GRUC_NEED(raw);
+        a->raw = cp->raw;
+    }
+#undef GRUC_NEED
+    const int64_t need = (int64_t)ggr_gru_conv_workspace_bytes(cp);
+    if (cp->workspace_bytes < need || (need > 0 && !cp->workspace))
+        return fail(GGR_E_INVALID, "GgrGruConvPass.workspace_bytes %lld is smaller than the %lld bytes the pass needs", (long long)cp->workspace_bytes, (long long)need);
+    const void* used[] = {a->a, a->x, a->w_h, a->w_x, a->bias, a->h, a->z, a->rh, a->out_h, a->raw, cp->workspace};
+    uintptr_t bits = 0;
+    for (const void* p : used) bits |= (uintptr_t)p;
+    if ((bits & 3u) != 0) return fail(GGR_E_INVALID, "GgrGruConvPass: a buffer is misaligned (every array needs 4-byte alignment)");
+    return GGR_OK;
+}
+}  // namespace
+
+size_t ggr_gru_conv_workspace_bytes(const GgrGruConvPass* cp) {
+    (void)cp;
+    return 0;       // the sum of an output element stays inside one wave: nothing passes through memory
+}
+
+int ggr_gru_conv_forward(const GgrGruConvPass* cp, void* stream) {
+    g_err[0] = 0;
+    ggr::GruConvArgs a;
+    const int rc = gru_conv_pass_check(cp, &a);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ggr::launch_gru_conv(a, s);
+    KCHECK(false, s, "gru_conv_forward");
+    return GGR_OK;
+}
 
 // ---- the distortion pass (blend_dist.hip): the depth-distortion plane over a forward's lists, and its backward -----------------
 namespace {

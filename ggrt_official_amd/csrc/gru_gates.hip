@@ -13,29 +13,16 @@
 // The grid is capped and strides over the rest.  No pointer is __restrict__: an output may be the very array of an input of the
 // same call (a lane reads its elements before it writes them); only h' over h is refused, by the entry point.
 #include "gru_gates.h"
-#include <float.h>
-#include <math.h>
+#include "gru_math.h"
 
 namespace ggr {
 namespace {
 
 constexpr int NT = kGruThreads;
 
-// exp(-|a|) with results below the smallest normal float taken as 0, whatever the denormal mode: from |a| = 87.4 on the sigmoid is
-// exactly 0 or 1, and neither it nor the tanh can overflow or turn NaN for a finite a.
-__device__ __forceinline__ float sigmoid_f(float a) {
-    float e = expf(-fabsf(a));
-    e = e < FLT_MIN ? 0.f : e;
-    const float p = 1.f / (1.f + e);
-    return a >= 0.f ? p : e * p;
-}
-
-// tanh|a| = (1 - e) / (1 + e) with e = exp(-2|a|), formed as -m / (2 + m) from m = expm1(-2|a|) so that small |a| lose nothing;
-// m is exactly -1 from |a| = 9.1 on, and the tanh exactly 1.
-__device__ __forceinline__ float tanh_f(float a) {
-    const float m = expm1f(-2.f * fabsf(a));
-    return copysignf(-m / (2.f + m), a);
-}
+// (the sigmoid and the tanh: gru_math.h, shared with the inference route's epilogues in gru_conv.hip)
+__device__ __forceinline__ float sigmoid_f(float a) { return gru_sigmoid(a); }
+__device__ __forceinline__ float tanh_f(float a) { return gru_tanh(a); }
 
 template <int V> __device__ __forceinline__ void ld(const float* p, float* v) {
     if constexpr (V == 4) {

@@ -27,6 +27,7 @@ Reference quirks kept on purpose (drop-in parity):
 """
 from __future__ import annotations
 
+import itertools
 import os
 from dataclasses import dataclass
 from math import isqrt
@@ -1502,7 +1503,19 @@ def fused_gru_half(h: Tensor, x: Tensor, w_zr_h: Tensor, w_zr_x: Tensor, b_zr: O
 
     Refused with a ValueError that names the argument: a dtype other than float32, a CPU tensor, inputs on different devices, ``h``
     and ``x`` that differ in batch or spatial size, weights or biases whose shapes do not fit Ch / Cx / the padding, an empty batch."""
-    fn = "fused_gru_half"
+    ph, pw = _gru_half_check("fused_gru_half", h, x, w_zr_h, w_zr_x, b_zr, w_q_h, w_q_x, b_q, padding)
+    h, x = h.contiguous(), x.contiguous()
+    conv = torch.nn.functional.conv2d
+    a_zr_h = conv(h, w_zr_h, None, padding=(ph, pw))
+    a_zr_x = conv(x, w_zr_x, b_zr, padding=(ph, pw))
+    a_q_x = conv(x, w_q_x, b_q, padding=(ph, pw))
+    z, rh = _GruGate.apply(a_zr_h.contiguous(), a_zr_x.contiguous(), h)
+    a_q_h = conv(rh, w_q_h, None, padding=(ph, pw))
+    return _GruBlend.apply(a_q_h.contiguous(), a_q_x.contiguous(), z, h)
+
+
+def _gru_half_check(fn, h, x, w_zr_h, w_zr_x, b_zr, w_q_h, w_q_x, b_q, padding):
+    """The refusals that `fused_gru_half` and `fused_gru_half_inference` share → the padding as two ints."""
     tensors = [("h", h), ("x", x), ("w_zr_h", w_zr_h), ("w_zr_x", w_zr_x), ("b_zr", b_zr), ("w_q_h", w_q_h), ("w_q_x", w_q_x), ("b_q", b_q)]
     for name, t in tensors:
         if not (torch.is_tensor(t) or (t is None and name.startswith("b_"))):
@@ -1536,14 +1549,121 @@ def fused_gru_half(h: Tensor, x: Tensor, w_zr_h: Tensor, w_zr_x: Tensor, b_zr: O
             raise ValueError(f"{fn}: {name} {tuple(t.shape)} is not {want} (Ch = {ch}, Cx = {cx}, padding {(ph, pw)}); {_GRU_TORCH_ROUTE}")
     if 2 * h.numel() >= 2 ** 31:
         raise ValueError(f"{fn}: h {tuple(h.shape)} is more than the kernels index (N * 2 * Ch * H * W must stay below 2^31); {_GRU_TORCH_ROUTE}")
-    h, x = h.contiguous(), x.contiguous()
-    conv = torch.nn.functional.conv2d
-    a_zr_h = conv(h, w_zr_h, None, padding=(ph, pw))
-    a_zr_x = conv(x, w_zr_x, b_zr, padding=(ph, pw))
-    a_q_x = conv(x, w_q_x, b_q, padding=(ph, pw))
-    z, rh = _GruGate.apply(a_zr_h.contiguous(), a_zr_x.contiguous(), h)
-    a_q_h = conv(rh, w_q_h, None, padding=(ph, pw))
-    return _GruBlend.apply(a_q_h.contiguous(), a_q_x.contiguous(), z, h)
+    return ph, pw
+
+
+_GRU_TRAINING_ROUTE = "use fused_gru_half (torch's convolutions, which autograd differentiates) for that call"
+
+
+def _gru_conv_refusals(fn, named, kh, kw):
+    """What the forward-only convolution kernels (csrc/gru_conv.hip) refuse beyond the shapes: a gradient, kernel sides they do not have."""
+    if torch.is_grad_enabled():
+        for name, t in named:
+            if t is not None and t.requires_grad:
+                raise ValueError(f"{fn}: {name} requires grad and grad mode is on: this route is forward only; {_GRU_TRAINING_ROUTE}")
+    if kh > 5 or kw > 5 or kh % 2 == 0 or kw % 2 == 0:
+        raise ValueError(f"{fn}: the padding gives a {kh} x {kw} kernel; the kernels take odd sides up to 5; {_GRU_TRAINING_ROUTE}")
+
+
+def _gru_conv_call(dev, dims, kernel, epilogue, out_channels=0, **pointers):
+    n, ch, cx, hh, ww = dims
+    cp = _lib.gru_conv_pass(reserved=0, batch=n, channels=ch, in_channels=cx, height=hh, width=ww, kernel_h=kernel[0], kernel_w=kernel[1],
+                            epilogue=epilogue, out_channels=out_channels, workspace=None, workspace_bytes=0, **pointers)
+    lib = _lib.load()
+    need = int(lib.ggr_gru_conv_workspace_bytes(C.byref(cp)))
+    workspace = None
+    if need:            # (0 today: the kernels pass nothing through memory)
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        cp.workspace, cp.workspace_bytes = workspace.data_ptr(), need
+    with torch.cuda.device(dev):
+        rc = lib.ggr_gru_conv_forward(C.byref(cp), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"ggr_gru_conv_forward failed (code {rc}): {_lib.last_error()}")
+
+
+def fused_gru_half_inference(h: Tensor, x: Tensor, w_zr_h: Tensor, w_zr_x: Tensor, b_zr: Optional[Tensor], w_q_h: Tensor, w_q_x: Tensor,
+                             b_q: Optional[Tensor], padding) -> Tensor:
+    """`fused_gru_half` for a call that needs no gradient, with the convolutions in HIP as well: two launches of
+    an implicit GEMM on the exact float32 MFMA (``GgrGruConvPass`` in include/ggr_raster.h) — GATE convolves ``h`` and ``x`` with the
+    z/r weights and writes ``z`` and ``r·h``, BLEND convolves ``r·h`` and ``x`` with the q weights and writes ``h'``.  The
+    pre-activations are never stored, the weights are read in place, nothing is cached and there is no autograd graph.  The same
+    arguments and the same function as `fused_gru_half` up to float32 summation order.
+
+    Refused as `fused_gru_half` refuses, and also, with a ValueError that names `fused_gru_half` as the route to take: a tensor
+    argument that requires grad while grad mode is on, and a padding that makes a kernel side even or above 5."""
+    fn = "fused_gru_half_inference"
+    ph, pw = _gru_half_check(fn, h, x, w_zr_h, w_zr_x, b_zr, w_q_h, w_q_x, b_q, padding)
+    named = (("h", h), ("x", x), ("w_zr_h", w_zr_h), ("w_zr_x", w_zr_x), ("b_zr", b_zr), ("w_q_h", w_q_h), ("w_q_x", w_q_x), ("b_q", b_q))
+    kernel = (2 * ph + 1, 2 * pw + 1)
+    _gru_conv_refusals(fn, named, *kernel)
+    with torch.no_grad():
+        h, x, w_zr_h, w_zr_x, w_q_h, w_q_x = (t.detach().contiguous() for t in (h, x, w_zr_h, w_zr_x, w_q_h, w_q_x))
+        b_zr, b_q = (t.detach().contiguous() if t is not None else None for t in (b_zr, b_q))
+        dev, shape = h.device, tuple(int(v) for v in h.shape)
+        dims = (shape[0], shape[1], int(x.shape[1]), shape[2], shape[3])
+        z, rh, out = (_image_loss_buffer(shape, dev) for _ in range(3))
+        _gru_conv_call(dev, dims, kernel, _lib.GRU_CONV_GATE, a=h.data_ptr(), x=x.data_ptr(), w_h=w_zr_h.data_ptr(), w_x=w_zr_x.data_ptr(),
+                       bias=_gru_ptr(b_zr), h=h.data_ptr(), z=z.data_ptr(), rh=rh.data_ptr())
+        _gru_conv_call(dev, dims, kernel, _lib.GRU_CONV_BLEND, a=rh.data_ptr(), x=x.data_ptr(), w_h=w_q_h.data_ptr(), w_x=w_q_x.data_ptr(),
+                       bias=_gru_ptr(b_q), h=h.data_ptr(), z=z.data_ptr(), out_h=out.data_ptr())
+    return out
+
+
+def gru_conv(a: Tensor, x: Tensor, w_h: Tensor, w_x: Tensor, bias: Optional[Tensor], padding) -> Tensor:
+    """The split-input convolution of the GRU kernels alone (the RAW epilogue of ``GgrGruConvPass``), forward only::
+
+        acc = conv2d(a, w_h, None, padding=padding) + conv2d(x, w_x, bias, padding=padding)
+
+    in one HIP launch, without a ``cat`` — for a host that arranges its own tail.  ``a`` [N,Ca,H,W], ``x`` [N,Cx,H,W], ``w_h``
+    [Cout,Ca,kh,kw], ``w_x`` [Cout,Cx,kh,kw], ``bias`` [Cout] or None, ``padding`` = ((kh−1)/2, (kw−1)/2) with odd sides up to 5
+    → [N,Cout,H,W].  Exact float32 arithmetic in a fixed order: two calls give the same bits.  Refused with a ValueError that names
+    the argument: what `fused_gru_half_inference` refuses, for these arguments."""
+    fn = "gru_conv"
+    tensors = [("a", a), ("x", x), ("w_h", w_h), ("w_x", w_x), ("bias", bias)]
+    for name, t in tensors:
+        if not (torch.is_tensor(t) or (t is None and name == "bias")):
+            raise ValueError(f"{fn}: {name} is not a tensor; {_GRU_TRAINING_ROUTE}")
+    tensors = [(name, t) for name, t in tensors if t is not None]
+    for name, t in tensors:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{fn}: {name} is {t.dtype}, not torch.float32; {_GRU_TRAINING_ROUTE}")
+    for name, t in tensors:
+        if t.device.type != "cuda":
+            raise ValueError(f"{fn}: {name} is on {t.device}; the kernels run on the GPU only (there is no CPU fallback); {_GRU_TRAINING_ROUTE}")
+    for name, t in tensors:
+        if t.device != a.device:
+            raise ValueError(f"{fn}: {name} is on {t.device}, a on {a.device}: the inputs are not on one device; {_GRU_TRAINING_ROUTE}")
+    if a.dim() != 4 or x.dim() != 4:
+        raise ValueError(f"{fn}: a {tuple(a.shape)} and x {tuple(x.shape)} are not [N, Ca, H, W] and [N, Cx, H, W]; {_GRU_TRAINING_ROUTE}")
+    if a.shape[0] != x.shape[0] or tuple(a.shape[2:]) != tuple(x.shape[2:]):
+        raise ValueError(f"{fn}: x {tuple(x.shape)} does not have a's batch and spatial sizes {tuple(a.shape)}; {_GRU_TRAINING_ROUTE}")
+    if a.numel() == 0 or x.numel() == 0:
+        raise ValueError(f"{fn}: a {tuple(a.shape)} or x {tuple(x.shape)} is empty; {_GRU_TRAINING_ROUTE}")
+    try:
+        ph, pw = (int(v) for v in padding)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: padding {padding!r} is not a (rows, columns) pair; {_GRU_TRAINING_ROUTE}") from None
+    if ph < 0 or pw < 0:
+        raise ValueError(f"{fn}: padding {padding!r} is negative; {_GRU_TRAINING_ROUTE}")
+    ca, cx, kh, kw = int(a.shape[1]), int(x.shape[1]), 2 * ph + 1, 2 * pw + 1
+    if w_h.dim() != 4 or w_h.shape[0] < 1 or tuple(w_h.shape[1:]) != (ca, kh, kw):
+        raise ValueError(f"{fn}: w_h {tuple(w_h.shape)} is not [Cout, {ca}, {kh}, {kw}] (Ca = {ca}, padding {(ph, pw)}); {_GRU_TRAINING_ROUTE}")
+    cout = int(w_h.shape[0])
+    for name, t, want in (("w_x", w_x, (cout, cx, kh, kw)), ("bias", bias, (cout,))):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{fn}: {name} {tuple(t.shape)} is not {want} (Cout = {cout}, Cx = {cx}, padding {(ph, pw)}); {_GRU_TRAINING_ROUTE}")
+    n, hh, ww = int(a.shape[0]), int(a.shape[2]), int(a.shape[3])
+    if n * hh * ww * max(2 * ca, cx, cout) >= 2 ** 31:
+        raise ValueError(f"{fn}: a {tuple(a.shape)} with {cx} and {cout} channels beside it is more than the kernels index (every array must stay "
+                         f"below 2^31 elements, a's twice over); {_GRU_TRAINING_ROUTE}")
+    _gru_conv_refusals(fn, tensors, kh, kw)
+    with torch.no_grad():
+        a, x, w_h, w_x = (t.detach().contiguous() for t in (a, x, w_h, w_x))
+        bias = bias.detach().contiguous() if bias is not None else None
+        out = _image_loss_buffer((n, cout, hh, ww), a.device)
+        _gru_conv_call(a.device, (n, ca, cx, hh, ww), (kh, kw), _lib.GRU_CONV_RAW, out_channels=cout, a=a.data_ptr(), x=x.data_ptr(),
+                       w_h=w_h.data_ptr(), w_x=w_x.data_ptr(), bias=_gru_ptr(bias), raw=out.data_ptr())
+    return out
 
 
 class _FusedGRU(nn.Module):
@@ -1551,11 +1671,12 @@ class _FusedGRU(nn.Module):
     module names, kernel shape, padding) in the order the reference applies them."""
     HALVES: tuple = ()
 
-    def __init__(self, hidden_dim: int = 128, input_dim: int = 192 + 128):
+    def __init__(self, hidden_dim: int = 128, input_dim: int = 192 + 128, *, hip_convs: bool = False):
         super().__init__()
         if not (isinstance(hidden_dim, int) and isinstance(input_dim, int) and hidden_dim >= 1 and input_dim >= 1):
             raise ValueError(f"{type(self).__name__}: hidden_dim {hidden_dim!r} and input_dim {input_dim!r} are not positive ints")
         self.hidden_dim, self.input_dim = hidden_dim, input_dim
+        self.hip_convs = bool(hip_convs)
         ch, cx = hidden_dim, input_dim
         init = {}
         for s, (kh, kw), pad in self.HALVES:
@@ -1603,10 +1724,18 @@ class _FusedGRU(nn.Module):
         return out
 
     def forward(self, h: Tensor, x: Tensor) -> Tensor:
+        """With ``hip_convs=True`` a call in which no gradient can be wanted — grad mode off, or neither ``h``, ``x`` nor a parameter
+        requires grad — takes `fused_gru_half_inference` (the convolutions in HIP too); every other call, and every call of a module
+        built with the default ``hip_convs=False``, takes `fused_gru_half`.  The two routes compute the same function up to float32
+        summation order."""
         if torch.is_tensor(x):
             x = x.contiguous()
+        half = fused_gru_half
+        if self.hip_convs and not (torch.is_grad_enabled() and any(
+                torch.is_tensor(t) and t.requires_grad for t in itertools.chain((h, x), self.parameters()))):
+            half = fused_gru_half_inference
         for s, _, pad in self.HALVES:
-            h = fused_gru_half(h, x, *(getattr(self, name + s) for name in ("w_zr_h", "w_zr_x", "b_zr", "w_q_h", "w_q_x", "b_q")), pad)
+            h = half(h, x, *(getattr(self, name + s) for name in ("w_zr_h", "w_zr_x", "b_zr", "w_q_h", "w_q_x", "b_q")), pad)
         return h
 
 
@@ -1614,7 +1743,8 @@ class FusedSepConvGRU(_FusedGRU):
     """GGRt's ``SepConvGRU`` (``ggrt/optimizer.py:51-78``): a horizontal 1×5 half-step, then a vertical 5×1 one, each four torch
     convolutions and two HIP launches.  Parameters per half (suffix 1, 2): ``w_zr_h``, ``w_zr_x``, ``b_zr``,
     ``w_q_h``, ``w_q_x``, ``b_q``.  ``forward(h, x)`` as the reference's; checkpoints move both ways through
-    ``load_reference_state_dict`` / ``reference_state_dict``."""
+    ``load_reference_state_dict`` / ``reference_state_dict``.  ``hip_convs=True`` (keyword only; a checkpoint does not know it): calls
+    that need no gradient run their convolutions in HIP as well, two launches per half-step."""
     HALVES = (("1", (1, 5), (0, 2)), ("2", (5, 1), (2, 0)))
 
 

@@ -1430,6 +1430,69 @@ int ggr_gru_blend_forward(const GgrGruPass* pass, void* stream);
 int ggr_gru_blend_backward(const GgrGruPass* pass, void* stream);
 int ggr_gru_gate_backward(const GgrGruPass* pass, void* stream);
 
+/* The convolutions of one ConvGRU half-step WITH its gate math, forward only: what an inference frame pays for (DepthPoseNet in
+ * .eval() under no_grad).  One implicit GEMM on the exact float32 MFMA per call, float32 dense NCHW maps, weights read in place
+ * in torch's [Cout,Cin,kh,kw] layout; the two inputs of the reference's cat[h, x] stay two tensors.  For every sample n, output
+ * channel co and pixel (y, x), with pad = ((kh - 1) / 2, (kw - 1) / 2), stride 1, zero padding, cross-correlation (F.conv2d):
+ *     acc[n, co, y, x] = bias[co] + sum_{ci < Ch, t} w_h[co, ci, t] a[n, ci, (y, x) + t - pad]
+ *                                 + sum_{ci < Cx, t} w_x[co, ci, t] x[n, ci, (y, x) + t - pad]
+ * and one of three epilogues, evaluated on the accumulators (the pre-activations are never stored):
+ *   GGR_GRU_CONV_GATE    a = h, w_h = w_zr_h [2Ch,Ch,kh,kw], w_x = w_zr_x [2Ch,Cx,kh,kw], bias = b_zr [2Ch] (z rows, then r rows):
+ *                        z = sigmoid(acc[:, :Ch])     rh = sigmoid(acc[:, Ch:]) h
+ *                        reads a, x, w_h, w_x, bias (or NULL), h; writes z, rh whole.
+ *   GGR_GRU_CONV_BLEND   a = rh, w_h = w_q_h [Ch,Ch,kh,kw], w_x = w_q_x [Ch,Cx,kh,kw], bias = b_q [Ch]:
+ *                        out_h = (1 - z) h + z tanh(acc)
+ *                        reads a, x, w_h, w_x, bias (or NULL), z, h; writes out_h whole.  out_h must not be h.
+ *   GGR_GRU_CONV_RAW     raw = acc, [N,out_channels,H,W]: the split-input convolution alone, w_h [out_channels,Ch,kh,kw],
+ *                        w_x [out_channels,Cx,kh,kw], bias [out_channels] or NULL.
+ *                        reads a, x, w_h, w_x, bias; writes raw whole.
+ * GATE then BLEND on the same h, x is one half-step of SepConvGRU (1 x 5, then 5 x 1) or the step of ConvGRU (3 x 3): the same
+ * function as GATE / BLEND of GgrGruPass behind the host's convolutions, up to float32 summation order.  sigmoid and tanh are
+ * those of GgrGruPass (exactly 0, 1, +-1 at |acc| = 100).  Any odd kernel sides up to 5, any sizes from 1 (a width below the
+ * kernel's clips every tap but the centre's); a tap never reads the neighbouring row or sample.
+ * An output must not overlap a or x (other workgroups still read them).  Per output element the sum runs in four k-ordered
+ * float32 chains — (a side, x side) x (alternate k pairs of every 32) — added in a fixed order: two calls give the same bits.
+ * One launch per call, no atomics, nothing to zero, no workspace (ggr_gru_conv_workspace_bytes returns 0; `workspace` may be
+ * NULL), nothing kept between calls.  The calls allocate nothing, read nothing back, are ordered on `stream`, do not synchronise
+ * and are hipGraph-capturable.
+ * GGR_E_INVALID, before anything is enqueued, for a struct_size smaller than the struct, a nonzero reserved field, batch,
+ * channels, in_channels, height, width (or, for RAW, out_channels) below 1, a kernel side that is even, below 1 or above 5, an
+ * unknown epilogue, N 2 Ch H W >= 2^31 (or any other array of the call beyond 2^31 - 1 elements), a NULL required pointer,
+ * out_h == h, workspace_bytes below what ggr_gru_conv_workspace_bytes returns, and a buffer that is not 4-byte aligned.  A
+ * pointer that the epilogue does not name above is not looked at. */
+#define GGR_GRU_CONV_GATE 0
+#define GGR_GRU_CONV_BLEND 1
+#define GGR_GRU_CONV_RAW 2
+typedef struct GgrGruConvPass {
+    int32_t struct_size;            /* sizeof(GgrGruConvPass) */
+    int32_t reserved;               /* 0 */
+    int32_t batch;                  /* N >= 1 */
+    int32_t channels;               /* Ch >= 1: the channels of a (and of h, z, rh, out_h) */
+    int32_t in_channels;            /* Cx >= 1: the channels of x */
+    int32_t height;                 /* H >= 1 */
+    int32_t width;                  /* W >= 1 */
+    int32_t kernel_h;               /* 1, 3 or 5 */
+    int32_t kernel_w;               /* 1, 3 or 5 */
+    int32_t epilogue;               /* GGR_GRU_CONV_GATE, _BLEND or _RAW */
+    int32_t out_channels;           /* RAW: the rows of w_h, w_x, bias and the channels of raw; GATE (2 Ch) and BLEND (Ch) ignore it */
+    const float* a;                 /* [N,Ch,H,W]: h for GATE, rh for BLEND */
+    const float* x;                 /* [N,Cx,H,W] */
+    const float* w_h;               /* [Cout,Ch,kh,kw] */
+    const float* w_x;               /* [Cout,Cx,kh,kw] */
+    const float* bias;              /* [Cout] or NULL */
+    const float* h;                 /* [N,Ch,H,W]: GATE, BLEND */
+    float* z;                       /* [N,Ch,H,W]: written by GATE, read by BLEND */
+    float* rh;                      /* [N,Ch,H,W]: written by GATE */
+    float* out_h;                   /* [N,Ch,H,W]: h', written by BLEND */
+    float* raw;                     /* [N,out_channels,H,W]: written by RAW */
+    void* workspace;                /* ggr_gru_conv_workspace_bytes(pass) bytes, or NULL where that is 0 */
+    int64_t workspace_bytes;        /* >= ggr_gru_conv_workspace_bytes(pass) */
+} GgrGruConvPass;
+
+/* bytes of GgrGruConvPass.workspace: 0 for every pass (the sum is not split across workgroups); also 0 for a NULL pass */
+size_t ggr_gru_conv_workspace_bytes(const GgrGruConvPass* pass);
+int ggr_gru_conv_forward(const GgrGruConvPass* pass, void* stream);
+
 /* The per-view camera quantities of the call site in one launch (cuda_splatting.py:18-46,66-73,82-89 and
  * ggrt/geometry/projection.py:233-247): for each of n views  scale = scale_invariant ? 1/near : 1,
  * view = inverse(extrinsics with its translation·scale)^T, full = view @ P^T with GGRt's projection P (built from
