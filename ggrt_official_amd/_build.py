@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libggr_raster.so")
 SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "tile_lists.hip", "tile_sort.hip", "blend_fwd.hip", "blend_bwd.hip", "blend_feat.hip", "blend_contrib.hip",
            "blend_pick.hip", "blend_dist.hip", "blend_absgrad.hip", "blend_hits.hip", "blend_hits_grad.hip", "projection.hip", "adapter.hip", "depth_head.hip", "epipolar.hip", "epipolar_attn.hip", "epipolar_attn_enc.hip", "image_loss.hip", "photometric_loss.hip", "warp_cost.hip", "upsample_depth.hip", "gru_gates.hip", "gru_conv.hip", "preprocess_bwd.hip", "camera.hip", "util.hip"]
-HEADERS = ["ggr_common.h", "blend_common.h", "blend_butterfly.h", "blend_feat.h", "blend_contrib.h", "blend_pick.h", "blend_dist.h", "blend_absgrad.h", "blend_hits.h", "blend_hits_grad.h", "projection.h", "adapter.h", "depth_head.h", "epipolar.h", "epipolar_attn.h", "epipolar_attn_enc.h", "image_loss.h", "photometric_loss.h", "warp_cost.h", "upsample_depth.h", "gru_gates.h", "gru_math.h", "gru_conv.h", "tile_sort.h", "sh_stage.h", "sh_terms.h", os.path.join("..", "..", "include", "ggr_raster.h")]
+HEADERS = ["ggr_common.h", "blend_common.h", "blend_butterfly.h", "blend_feat.h", "blend_contrib.h", "blend_pick.h", "blend_dist.h", "blend_absgrad.h", "blend_hits.h", "blend_hits_grad.h", "projection.h", "adapter.h", "depth_head.h", "epipolar.h", "epipolar_attn.h", "epipolar_attn_enc.h", "image_loss.h", "photometric_loss.h", "warp_cost.h", "warp_geometry.h", "block_reduce.h", "upsample_depth.h", "gru_gates.h", "gru_math.h", "gru_conv.h", "tile_sort.h", "sh_stage.h", "sh_terms.h", os.path.join("..", "..", "include", "ggr_raster.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"]
 # per-file additions.  The blend kernels are VALU-bound and the SLP vectoriser packs their fp32 math into v_pk_*

@@ -16,6 +16,7 @@
 // 52-wide array (at most 10 lanes two-way).  Forward 25 472 bytes a workgroup at window 11 (6 per CU), backward 45 216 (3 per CU):
 // the derivative maps live where the image tiles were, which are dead after the first row pass.
 #include "image_loss.h"
+#include "block_reduce.h"
 #include <math.h>
 
 namespace ggr {
@@ -128,28 +129,6 @@ __device__ __forceinline__ Stats col_pass5(const ImageLossArgs& a, const float* 
 
 __device__ __forceinline__ float c1() { return (float)(0.01 * 0.01); }
 __device__ __forceinline__ float c2() { return (float)(0.03 * 0.03); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// the sums of `n` values per thread over the workgroup, in a fixed order; valid in thread 0
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double (*sred)[NT / 64]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int q = 0; q < N; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) sred[q][wave] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int q = 0; q < N; ++q) {
-            double s = sred[q][0];
-            for (int w = 1; w < NT / 64; ++w) s += sred[q][w];
-            v[q] = s;
-        }
-}
 
 template <int R>
 __global__ __launch_bounds__(NT) void image_loss_fwd_kernel(const ImageLossArgs a) {

@@ -28,7 +28,15 @@
 //     dL/dinv_depths is written once.
 //   2 one workgroup per (iteration, view): adds the 12 sums over the tiles in a fixed order and chains them into the six numbers.
 // No atomics, fixed summation orders: two runs give the same bits.
+//
+// The camera model — Kinv, the pose, project, the bilinear taps, the projection's backward and the pose chain — is warp_geometry.h's,
+// shared with warp_cost.hip; the double sums are block_reduce.h's.  `project` and `taps_at` are compiled without contraction, so the
+// backward's two call sites (the halo loop that fills sx, the per-pixel gradient loop) and the forward perform the same IEEE
+// operations and land in the same bilinear cell.  This file keeps what is the loss's own: tiles, halos, reflection, SSIM, the
+// statistics, the selection, the finish and the smoothness terms.
 #include "photometric_loss.h"
+#include "block_reduce.h"
+#include "warp_geometry.h"
 #include <math.h>
 
 namespace ggr {
@@ -49,8 +57,6 @@ constexpr int H1 = TH + 2, W1 = TW + 2, N1 = H1 * W1;       // the tile with a h
 constexpr int H2 = TH + 4, W2 = TW + 4, N2 = H2 * W2;       // the tile with a halo of 2
 constexpr int PIX = TH * TW / NT;                            // pixels of the tile per thread
 
-struct Cam { float Kinv[9], R[9], t[3], Kr[9]; };
-
 // ReflectionPad2d(1) as an index; clamped, so that a partial tile's overhang (whose values nobody uses) stays inside the plane
 __device__ __forceinline__ int reflect(int y, int n) {
     y = y < 0 ? -y : y;
@@ -58,74 +64,11 @@ __device__ __forceinline__ int reflect(int y, int n) {
     return min(max(y, 0), n - 1);
 }
 
-// Camera.Kinv (a clone of K with four entries replaced), Pose.from_vec (R = Rx Ry Rz of the Euler angles, translation first)
-// and the view's intrinsics
+// the target camera's Kinv, the pose of (iteration i, view j) and the view's intrinsics
 __device__ void setup_cam(const PhotoLossArgs& a, int i, int j, Cam* c) {
-    const float* K = a.K;
-    for (int k = 0; k < 9; ++k) c->Kinv[k] = K[k];
-    c->Kinv[0] = 1.f / K[0];
-    c->Kinv[4] = 1.f / K[4];
-    c->Kinv[2] = -1.f * K[2] / K[0];
-    c->Kinv[5] = -1.f * K[5] / K[4];
-    const float* p = a.poses + ((int64_t)j * a.n + i) * 6;
-    float sx, cx, sy, cy, sz, cz;
-    sincosf(p[3], &sx, &cx);
-    sincosf(p[4], &sy, &cy);
-    sincosf(p[5], &sz, &cz);
-    c->R[0] = cy * cz;                  c->R[1] = -cy * sz;                 c->R[2] = sy;
-    c->R[3] = cx * sz + sx * sy * cz;   c->R[4] = cx * cz - sx * sy * sz;   c->R[5] = -sx * cy;
-    c->R[6] = sx * sz - cx * sy * cz;   c->R[7] = sx * cz + cx * sy * sz;   c->R[8] = cx * cy;
-    c->t[0] = p[0]; c->t[1] = p[1]; c->t[2] = p[2];
+    kinv_closed_form(a.K, c->Kinv);
+    pose_from_vec(a.poses + ((int64_t)j * a.n + i) * 6, c->R, c->t);
     for (int k = 0; k < 9; ++k) c->Kr[k] = a.ref_Ks[(int64_t)j * 9 + k];
-}
-
-struct Proj { float depth, ray[3], X[3], P2, Z, u, v; };
-
-// inv2depth, Camera.reconstruct (the target camera's pose is the identity), Camera.project with its Z.clamp(min=1e-5); the
-// normalisation 2x/(W-1) - 1 and grid_sample's align_corners=True undo each other: (u, v) is the sample position in pixels
-__device__ __forceinline__ Proj project(const Cam& c, float d, int qx, int qy) {
-    Proj r;
-    r.depth = d <= 0.f ? 0.f : 1.f / fmaxf(d, 1e-6f);
-    const float x = (float)qx, y = (float)qy;
-    for (int k = 0; k < 3; ++k) {
-        r.ray[k] = c.Kinv[3 * k] * x + c.Kinv[3 * k + 1] * y + c.Kinv[3 * k + 2];
-        r.X[k] = r.ray[k] * r.depth;
-    }
-    float Y[3], P[3];
-    for (int k = 0; k < 3; ++k) Y[k] = c.R[3 * k] * r.X[0] + c.R[3 * k + 1] * r.X[1] + c.R[3 * k + 2] * r.X[2] + c.t[k];
-    for (int k = 0; k < 3; ++k) P[k] = c.Kr[3 * k] * Y[0] + c.Kr[3 * k + 1] * Y[1] + c.Kr[3 * k + 2] * Y[2];
-    r.P2 = P[2];
-    r.Z = fmaxf(P[2], 1e-5f);
-    r.u = P[0] / r.Z;
-    r.v = P[1] / r.Z;
-    return r;
-}
-
-// the four taps of grid_sample(bilinear, zeros, align_corners=True) at (u, v): offsets (-1 where the tap lies outside) and weights
-struct Taps { int64_t o00, o01, o10, o11; float wx0, wx1, wy0, wy1; };
-
-__device__ __forceinline__ Taps taps_at(float u, float v, int H, int W) {
-    Taps t;
-    t.o00 = t.o01 = t.o10 = t.o11 = -1;
-    t.wx0 = t.wx1 = t.wy0 = t.wy1 = 0.f;
-    if (!(u > -1.f && u < (float)W && v > -1.f && v < (float)H)) return t;     // (a NaN or an infinite coordinate samples nothing)
-    const float fx = floorf(u), fy = floorf(v);
-    const int ix = (int)fx, iy = (int)fy;
-    t.wx0 = (fx + 1.f) - u; t.wx1 = u - fx;
-    t.wy0 = (fy + 1.f) - v; t.wy1 = v - fy;
-    const bool x0 = ix >= 0, x1 = ix + 1 < W, y0 = iy >= 0, y1 = iy + 1 < H;
-    const int64_t base = (int64_t)iy * W + ix;
-    if (x0 && y0) t.o00 = base;
-    if (x1 && y0) t.o01 = base + 1;
-    if (x0 && y1) t.o10 = base + W;
-    if (x1 && y1) t.o11 = base + W + 1;
-    return t;
-}
-
-__device__ __forceinline__ float tap(const float* __restrict__ p, int64_t o) { return o >= 0 ? p[o] : 0.f; }
-
-__device__ __forceinline__ float sample(const float* __restrict__ p, const Taps& t) {
-    return tap(p, t.o00) * (t.wx0 * t.wy0) + tap(p, t.o01) * (t.wx1 * t.wy0) + tap(p, t.o10) * (t.wx0 * t.wy1) + tap(p, t.o11) * (t.wx1 * t.wy1);
 }
 
 // the 3 x 3 means of x and y, their variances and covariance, and what SSIM makes of them.  The reference forms the variances as
@@ -171,29 +114,6 @@ __device__ __forceinline__ Ssim ssim_of(const Stats& s, float C1, float C2) {
     r.B2 = s.sig1 + s.sig2 + C2;
     r.value = (r.A1 * r.A2) / (r.B1 * r.B2);
     return r;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// the sums of N values per thread over the workgroup, in a fixed order; valid in thread 0.  The caller synchronises before the
-// next use of `sred`.
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double (*sred)[NT / 64]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int q = 0; q < N; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) sred[q][wave] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int q = 0; q < N; ++q) {
-            double s = sred[q][0];
-            for (int w = 1; w < NT / 64; ++w) s += sred[q][w];
-            v[q] = s;
-        }
 }
 
 __device__ __forceinline__ void tile_origin(const PhotoLossArgs& a, int& y0, int& x0) {
@@ -506,7 +426,8 @@ __global__ __launch_bounds__(NT) void photo_bwd_kernel(const PhotoLossArgs a) {
                 gu += gw[ch] * (t.wy0 * (v01 - v00) + t.wy1 * (v11 - v10));
                 gv += gw[ch] * (t.wx0 * (v10 - v00) + t.wx1 * (v11 - v01));
             }
-            // u = P0 / Z, v = P1 / Z, Z = max(P2, 1e-5); P = Kr (R X + t); X = ray / inv_depth
+            // u = P0 / Z, v = P1 / Z, Z = max(P2, 1e-5); P = Kr (R X + t); X = ray / inv_depth.  Written out here and in
+            // warp_cost.hip, not a function of warp_geometry.h: as one it cost this kernel 8 VGPRs (174: two workgroups a CU, not three)
             float gP[3], gY[3], gX[3];
             gP[0] = gu / pr.Z;
             gP[1] = gv / pr.Z;
@@ -564,20 +485,8 @@ __global__ __launch_bounds__(NT) void photo_pose_kernel(const PhotoLossArgs a, c
     }
     block_sum(v, sred);
     if (threadIdx.x == 0) {
-        const float* p = a.poses + ((int64_t)j * a.n + i) * 6;
-        float* g = a.g_poses + ((int64_t)j * a.n + i) * 6;
-        const double sx = sin((double)p[3]), cx = cos((double)p[3]), sy = sin((double)p[4]), cy = cos((double)p[4]);
-        const double sz = sin((double)p[5]), cz = cos((double)p[5]);
-        const double R[9] = {cy * cz, -cy * sz, sy, cx * sz + sx * sy * cz, cx * cz - sx * sy * sz, -sx * cy,
-                             sx * sz - cx * sy * cz, sx * cz + cx * sy * sz, cx * cy};
-        // dR/dx: row 1 becomes -row 2, row 2 becomes row 1
-        const double gx = -(v[3] * R[6] + v[4] * R[7] + v[5] * R[8]) + (v[6] * R[3] + v[7] * R[4] + v[8] * R[5]);
-        const double gy = v[0] * (-sy * cz) + v[1] * (sy * sz) + v[2] * cy + v[3] * (sx * cy * cz) + v[4] * (-sx * cy * sz) + v[5] * (sx * sy) +
-                          v[6] * (-cx * cy * cz) + v[7] * (cx * cy * sz) + v[8] * (-cx * sy);
-        const double gz = v[0] * (-cy * sz) + v[1] * (-cy * cz) + v[3] * (cx * cz - sx * sy * sz) + v[4] * (-cx * sz - sx * sy * cz) +
-                          v[6] * (sx * cz + cx * sy * sz) + v[7] * (-sx * sz + cx * sy * cz);
-        g[0] = (float)v[9]; g[1] = (float)v[10]; g[2] = (float)v[11];
-        g[3] = (float)gx; g[4] = (float)gy; g[5] = (float)gz;
+        const int64_t o = ((int64_t)j * a.n + i) * 6;
+        pose_chain(v, a.poses + o, a.g_poses + o);
     }
 }
 

@@ -16,8 +16,12 @@
 //     (summed over the views in a register, written once).
 //   2 one workgroup per view: adds the 12 sums over the tiles in a fixed order and chains them into the six numbers.
 // Everything but dL/dfmaps_ref has a fixed order of summation: two runs give the same bits.  The backward calls the forward's own
-// `project` and `taps_at`, compiled without contraction, so it makes the forward's floor and clamp decisions without storing them.
+// `project` and `taps_at` (warp_geometry.h, shared with photometric_loss.hip), compiled without contraction, so it makes the
+// forward's floor and clamp decisions without storing them.  This file keeps what is the cost map's own: `scaled_K`, the folded
+// disparity, `tile_coordinates`, the channel split, the scatter with atomics and the LDS meeting of the eight waves.
 #include "warp_cost.h"
+#include "block_reduce.h"
+#include "warp_geometry.h"
 #include <math.h>
 
 namespace ggr {
@@ -30,8 +34,6 @@ namespace {
 constexpr int TP = kWarpTilePixels, G = kWarpGroups, NT = kWarpThreads, MV = kWarpMaxViews, CS = kWarpChannelSlice;
 constexpr int KPT = CS / G;     // forward: channels per thread
 
-struct Cam { float Kinv[9], R[9], t[3], Kr[9]; };
-
 // scale_intrinsics (Camera.scaled returns the camera itself for a factor of exactly 1)
 __device__ __forceinline__ void scaled_K(const float* K, float s, float* out) {
 #pragma clang fp contract(off)
@@ -43,84 +45,19 @@ __device__ __forceinline__ void scaled_K(const float* K, float s, float* out) {
     out[5] = (K[5] + 0.5f) * s - 0.5f;
 }
 
-// Camera.Kinv of the scaled target camera (a clone of K with four entries replaced), Pose.from_vec (R = Rx Ry Rz of the Euler angles,
-// translation first) and the view's scaled intrinsics
+// Camera.Kinv of the scaled target camera, the pose of view j and the view's scaled intrinsics
 __device__ void setup_cam(const WarpCostArgs& a, int j, Cam* c) {
-#pragma clang fp contract(off)
     float K[9];
     scaled_K(a.K, a.scale, K);
-    for (int k = 0; k < 9; ++k) c->Kinv[k] = K[k];
-    c->Kinv[0] = 1.f / K[0];
-    c->Kinv[4] = 1.f / K[4];
-    c->Kinv[2] = -1.f * K[2] / K[0];
-    c->Kinv[5] = -1.f * K[5] / K[4];
-    const float* p = a.poses + (int64_t)j * 6;
-    float sx, cx, sy, cy, sz, cz;
-    sincosf(p[3], &sx, &cx);
-    sincosf(p[4], &sy, &cy);
-    sincosf(p[5], &sz, &cz);
-    c->R[0] = cy * cz;                  c->R[1] = -cy * sz;                 c->R[2] = sy;
-    c->R[3] = cx * sz + sx * sy * cz;   c->R[4] = cx * cz - sx * sy * sz;   c->R[5] = -sx * cy;
-    c->R[6] = sx * sz - cx * sy * cz;   c->R[7] = sx * cz + cx * sy * sz;   c->R[8] = cx * cy;
-    c->t[0] = p[0]; c->t[1] = p[1]; c->t[2] = p[2];
+    kinv_closed_form(K, c->Kinv);
+    pose_from_vec(a.poses + (int64_t)j * 6, c->R, c->t);
     scaled_K(a.ref_Ks + (int64_t)j * 9, a.scale, c->Kr);
 }
 
-struct Proj { float d, depth, ray[3], X[3], P2, Z, u, v; };
-
-// disp_to_depth's affine map (when folded), inv2depth, Camera.reconstruct (the target camera's pose is the identity), Camera.project
-// with its Z.clamp(min=1e-5); the normalisation 2x/(w-1) - 1 and grid_sample's align_corners=True undo each other: (u, v) is the
-// sample position in pixels
-__device__ __forceinline__ Proj project(const WarpCostArgs& a, const Cam& c, float inv, int qx, int qy) {
+// disp_to_depth's affine map (when folded) in front of inv2depth
+__device__ __forceinline__ float inverse_depth(const WarpCostArgs& a, float inv) {
 #pragma clang fp contract(off)
-    Proj r;
-    r.d = a.disp_on ? a.disp_a + a.disp_b * inv : inv;
-    r.depth = r.d <= 0.f ? 0.f : 1.f / fmaxf(r.d, 1e-6f);
-    const float x = (float)qx, y = (float)qy;
-    for (int k = 0; k < 3; ++k) {
-        r.ray[k] = c.Kinv[3 * k] * x + c.Kinv[3 * k + 1] * y + c.Kinv[3 * k + 2];
-        r.X[k] = r.ray[k] * r.depth;
-    }
-    float Y[3], P[3];
-    for (int k = 0; k < 3; ++k) Y[k] = c.R[3 * k] * r.X[0] + c.R[3 * k + 1] * r.X[1] + c.R[3 * k + 2] * r.X[2] + c.t[k];
-    for (int k = 0; k < 3; ++k) P[k] = c.Kr[3 * k] * Y[0] + c.Kr[3 * k + 1] * Y[1] + c.Kr[3 * k + 2] * Y[2];
-    r.P2 = P[2];
-    r.Z = fmaxf(P[2], 1e-5f);
-    r.u = P[0] / r.Z;
-    r.v = P[1] / r.Z;
-    return r;
-}
-
-// the four taps of grid_sample(bilinear, zeros, align_corners=True) at (u, v): the cell, offsets (-1 where the tap lies outside) and
-// weights.  A sample that no tap of the map reaches (a NaN or an infinite coordinate too) has the cell (-2, -2).
-struct Taps { int ix, iy; int64_t o00, o01, o10, o11; float wx0, wx1, wy0, wy1; };
-
-__device__ __forceinline__ Taps taps_at(float u, float v, int H, int W) {
-#pragma clang fp contract(off)
-    Taps t;
-    t.ix = t.iy = -2;
-    t.o00 = t.o01 = t.o10 = t.o11 = -1;
-    t.wx0 = t.wx1 = t.wy0 = t.wy1 = 0.f;
-    if (!(u > -1.f && u < (float)W && v > -1.f && v < (float)H)) return t;
-    const float fx = floorf(u), fy = floorf(v);
-    const int ix = (int)fx, iy = (int)fy;
-    t.ix = ix; t.iy = iy;
-    t.wx0 = (fx + 1.f) - u; t.wx1 = u - fx;
-    t.wy0 = (fy + 1.f) - v; t.wy1 = v - fy;
-    const bool x0 = ix >= 0, x1 = ix + 1 < W, y0 = iy >= 0, y1 = iy + 1 < H;
-    const int64_t base = (int64_t)iy * W + ix;
-    if (x0 && y0) t.o00 = base;
-    if (x1 && y0) t.o01 = base + 1;
-    if (x0 && y1) t.o10 = base + W;
-    if (x1 && y1) t.o11 = base + W + 1;
-    return t;
-}
-
-__device__ __forceinline__ float tap(const float* __restrict__ p, int64_t o) { return o >= 0 ? p[o] : 0.f; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
+    return a.disp_on ? a.disp_a + a.disp_b * inv : inv;
 }
 
 // the sample coordinates of the tile's pixels for views v0 .. v0 + nv - 1, once per workgroup
@@ -134,7 +71,7 @@ __device__ __forceinline__ void tile_coordinates(const WarpCostArgs& a, int v0, 
         float u = 0.f, v = 0.f;
         if (q < hw) {
             const int y = (int)(q / a.w), x = (int)(q - (int64_t)y * a.w);
-            const Proj pr = project(a, cam[vi], a.inv_depth[q], x, y);
+            const Proj pr = project(cam[vi], inverse_depth(a, a.inv_depth[q]), x, y);
             u = pr.u;
             v = pr.v;
             if (write_cells) {
@@ -244,9 +181,11 @@ __global__ __launch_bounds__(NT) void warp_cost_bwd_kernel(const WarpCostArgs a)
                 gv = sGv[0][lane];
                 for (int k = 1; k < G; ++k) { gu += sGu[k][lane]; gv += sGv[k][lane]; }
                 if (gu != 0.f || gv != 0.f) {
-                    // u = P0 / Z, v = P1 / Z, Z = max(P2, 1e-5); P = Kr (R X + t); X = ray * depth
+                    const float d = inverse_depth(a, inv);
+                    // u = P0 / Z, v = P1 / Z, Z = max(P2, 1e-5); P = Kr (R X + t); X = ray * depth  (written out, as in
+                    // photometric_loss.hip: see there)
                     const Cam& c = cam[v];
-                    const Proj pr = project(a, c, inv, px, py);
+                    const Proj pr = project(c, d, px, py);
                     float gP[3], gY[3], gX[3];
                     gP[0] = gu / pr.Z;
                     gP[1] = gv / pr.Z;
@@ -258,7 +197,7 @@ __global__ __launch_bounds__(NT) void warp_cost_bwd_kernel(const WarpCostArgs a)
                         acc[9 + m] = (double)gY[m];
                     }
                     const float gdepth = gX[0] * pr.ray[0] + gX[1] * pr.ray[1] + gX[2] * pr.ray[2];
-                    if (pr.d >= 1e-6f) gd += -gdepth * pr.depth * pr.depth;     // (below the clamp, and at or below zero, the depth is a constant)
+                    if (d >= 1e-6f) gd += -gdepth * pr.depth * pr.depth;     // (below the clamp, and at or below zero, the depth is a constant)
                 }
             }
             if (a.g_poses) {
@@ -285,20 +224,7 @@ __global__ __launch_bounds__(TP) void warp_cost_pose_kernel(const WarpCostArgs a
     }
     for (int k = 0; k < kWarpPosePartials; ++k) v[k] = wave_sum(v[k]);
     if (threadIdx.x == 0) {
-        const float* p = a.poses + (int64_t)j * 6;
-        float* g = a.g_poses + (int64_t)j * 6;
-        const double sx = sin((double)p[3]), cx = cos((double)p[3]), sy = sin((double)p[4]), cy = cos((double)p[4]);
-        const double sz = sin((double)p[5]), cz = cos((double)p[5]);
-        const double R[9] = {cy * cz, -cy * sz, sy, cx * sz + sx * sy * cz, cx * cz - sx * sy * sz, -sx * cy,
-                             sx * sz - cx * sy * cz, sx * cz + cx * sy * sz, cx * cy};
-        // dR/dx: row 1 becomes -row 2, row 2 becomes row 1
-        const double gx = -(v[3] * R[6] + v[4] * R[7] + v[5] * R[8]) + (v[6] * R[3] + v[7] * R[4] + v[8] * R[5]);
-        const double gy = v[0] * (-sy * cz) + v[1] * (sy * sz) + v[2] * cy + v[3] * (sx * cy * cz) + v[4] * (-sx * cy * sz) + v[5] * (sx * sy) +
-                          v[6] * (-cx * cy * cz) + v[7] * (cx * cy * sz) + v[8] * (-cx * sy);
-        const double gz = v[0] * (-cy * sz) + v[1] * (-cy * cz) + v[3] * (cx * cz - sx * sy * sz) + v[4] * (-cx * sz - sx * sy * cz) +
-                          v[6] * (sx * cz + cx * sy * sz) + v[7] * (-sx * sz + cx * sy * cz);
-        g[0] = (float)v[9]; g[1] = (float)v[10]; g[2] = (float)v[11];
-        g[3] = (float)gx; g[4] = (float)gy; g[5] = (float)gz;
+        pose_chain(v, a.poses + (int64_t)j * 6, a.g_poses + (int64_t)j * 6);
     }
 }
 
